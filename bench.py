@@ -6,6 +6,17 @@ images/sec for the whole job (BASELINE.json metric).
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --model resnet20 | resnet50          (BASELINE.json configs 3 and 5)
     python bench.py --mode ps --gpus N                   (config 4: 1 ps + N workers, async)
+    python bench.py ... --dump-outputs DIR               (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, pre-warms, warms up, times the K steps and prints the result line - nothing else.
+``--full`` is where any further measurement of this script belongs (none today: the other models, modes
+and precisions are invocations of their own, the kernel and stock-PyTorch tables are bench/*.py).
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes the state the last step left - the fp32
+variables, their gradients, the loss / hit counters, the global step - as float32 / float64 .npy files
+(an array above 4 Mi elements as a fixed, seeded sample; under 64 MB in all).  Data, weights, batch sampling
+and dropout are seeded, and with this option the pre-warm runs a fixed number of steps instead of a fixed
+time, so two runs with the same arguments train through the same batches and can be compared array by array.
 
 Launching: under torchrun (``WORLD_SIZE`` set) each process is one rank.  Without
 ``WORLD_SIZE`` and with ``--gpus N > 1`` this process is a pure launcher: it starts N
@@ -56,6 +67,13 @@ def parse_args(argv=None):
                     "or WORLD_SIZE under torchrun")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever this script measures beyond the headline figure (nothing today; a plain "
+                         "run only sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (variables, gradients, loss / "
+                         "hit counters, global step) as DIR/<name>.npy; the pre-warm then runs a fixed number of "
+                         "steps, so runs with the same arguments are comparable array by array")
     ap.add_argument("--prewarm_ms", type=float, default=150.0,
                     help="before the W warmup steps, replay training steps for this long (GPU clock ramp; "
                          "reported as config.prewarm); 0 disables")
@@ -100,7 +118,10 @@ def parse_args(argv=None):
     ap.add_argument("--ps_verify", type=int, default=0, help=argparse.SUPPRESS)  # test hook, see bench_ps
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl = RCCL (one rank per GPU); gloo only to rehearse several ranks on one GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------- launcher
@@ -208,7 +229,38 @@ def _steps_per_graph(args, d) -> int:
     return 4 if d.world == 1 else 1
 
 
-def timed(runner, steps: int, warmup: int, d: Dist, prewarm_ms: float = 0.0):
+# --dump-outputs: pre-warm steps run instead of the --prewarm_ms of steps (about 150 ms of each workload's
+# step), so the step count - and with it every batch and dropout mask - repeats from run to run
+DUMP_PREWARM_STEPS = {"mnist_cnn": 800, "mnist_cnn_fp32": 100, "resnet20": 130, "resnet50": 10}
+DUMP_MAX_ELEMS = 4 << 20  # per array (16 MB of float32); no path dumps more than three arrays of that size
+
+
+def _dump_prewarm_steps(args) -> int:
+    if not args.dump_outputs or args.prewarm_ms <= 0:
+        return 0
+    key = args.model + ("_fp32" if args.model == "mnist_cnn" and args.dtype == "fp32" else "")
+    return DUMP_PREWARM_STEPS[key]
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Write every tensor of ``arrays`` as ``path/<name>.npy``: floating point as float32 (float64 stays),
+    integers as float64 (exact).  An array above DUMP_MAX_ELEMS elements is written as the flat elements at
+    DUMP_MAX_ELEMS sorted positions drawn once from a generator seeded with 0 (the same positions in every
+    run and every build)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        a = t.to(torch.float64 if wide else torch.float32).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def timed(runner, steps: int, warmup: int, d: Dist, prewarm_ms: float = 0.0, prewarm_steps: int = 0):
     """Pre-warm, W untimed steps, then exactly K steps between barrier+sync brackets.  Returns
     (elapsed_s max over ranks, per-window ms/step list measured on this rank, pre-warm steps).
 
@@ -217,7 +269,9 @@ def timed(runner, steps: int, warmup: int, d: Dist, prewarm_ms: float = 0.0):
     ramps its clocks over the first tens of ms of load: with the driver's W=5 / K=20 CNN run
     (1 + 4 ms of GPU work) the timed windows fell from 0.212 to 0.204 ms/step, after 100
     untimed steps they sat at 0.195-0.196 (profiles/r4_cnn_clock_ramp.txt).  The pre-warm
-    steps are real steps (they train the model) and are reported in the JSON config."""
+    steps are real steps (they train the model) and are reported in the JSON config.
+    ``prewarm_steps`` > 0 (--dump-outputs): the same chunks until that many steps have run,
+    whatever time they take."""
     run = runner.run if hasattr(runner, "run") else (lambda n: [runner() for _ in range(n)])
     S = getattr(runner, "steps", 1)
     pre = 0
@@ -228,7 +282,10 @@ def timed(runner, steps: int, warmup: int, d: Dist, prewarm_ms: float = 0.0):
             run(chunk)
             pre += chunk
             torch.cuda.synchronize()
-            if d.max(time.perf_counter() - t) * 1000.0 >= prewarm_ms:
+            if prewarm_steps > 0:
+                if pre >= prewarm_steps:
+                    break
+            elif d.max(time.perf_counter() - t) * 1000.0 >= prewarm_ms:
                 break
     if hasattr(runner, "prime"):  # graph captures happen here, never inside the timed steps
         pre += runner.prime()
@@ -359,9 +416,13 @@ def bench_cnn(args, d: Dist):
     runner = MultiStepGraph(step, spg, warmup=2,
                             enabled=((d.world == 1 or comm is not None) and not args.no_graph and graphs_enabled()),
                             capture_error_mode="thread_local", finish=trainer.join_side)
-    elapsed, win, pre = timed(runner, args.steps, args.warmup, d, args.prewarm_ms)
+    elapsed, win, pre = timed(runner, args.steps, args.warmup, d, args.prewarm_ms, _dump_prewarm_steps(args))
     if comm is not None and hasattr(comm, "check_health"):
         comm.check_health()
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"variables": trainer.P.master, "gradients": trainer.P.grad,
+                                         "loss_sum": trainer.loss_sum, "correct": trainer.correct,
+                                         "global_step": trainer.global_step})
     loss = float(trainer.loss_sum.item()) / B
     same = replicas_identical(trainer.P.master, d) if d.world > 1 else None
     ndev = d.distinct_devices()
@@ -432,7 +493,10 @@ def bench_resnet(args, d: Dist):
 
     runner = MultiStepGraph(step, _steps_per_graph(args, d), warmup=2, enabled=((d.world == 1 or comm is not None) and not args.no_graph
                                                 and graphs_enabled()), capture_error_mode="thread_local")
-    elapsed, win, pre = timed(runner, args.steps, args.warmup, d, args.prewarm_ms)
+    elapsed, win, pre = timed(runner, args.steps, args.warmup, d, args.prewarm_ms, _dump_prewarm_steps(args))
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"variables": prog.P.master, "gradients": prog.P.grad, "loss_sum": prog.loss,
+                                         "global_step": gstep})
     # trainable variables only: BN moving statistics are per-replica (each rank's own batches)
     train_vals = torch.cat([prog.P.view(n).reshape(-1) for n in names])
     same = replicas_identical(train_vals, d) if d.world > 1 else None
@@ -549,9 +613,14 @@ def bench_ps(args):
     if args.ps_verify:
         _ps_verify(args, run1, link, client, tr, shard_specs, dev, server)
 
-    elapsed, win, pre = timed(run1, args.steps, args.warmup, _D, args.prewarm_ms)
+    elapsed, win, pre = timed(run1, args.steps, args.warmup, _D, args.prewarm_ms, _dump_prewarm_steps(args))
     gs = link.host_reply()
     link.check()
+    if args.dump_outputs and idx == 0:
+        # worker 0's view: the variables as last pulled from the ps, its own last gradients and counters
+        # (repeatable with one worker; several workers' pushes are applied in arrival order)
+        dump_outputs(args.dump_outputs, {"variables": tr.P.master, "gradients": tr.P.grad,
+                                         "loss_sum": tr.loss_sum, "correct": tr.correct})
     loss = float(tr.loss_sum.item()) / B
     link.close()
     client.done()

@@ -67,6 +67,32 @@ def test_bench_eight_ranks(model, batch):
     assert cfg["global_batch"] == 8 * batch and cfg["parallelism"] == "dp8"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the state the last timed step left as float32 / float64 .npy files, under 64 MB;
+    the step count is prewarm + W + K exactly (the pre-warm is a fixed number of steps with this option, and
+    --steps sets the timed steps), and a second run with the same arguments - here with --full, which adds
+    nothing to the path - reproduces every array bit for bit (seeded data, weights, sampling and dropout;
+    the kernels' reductions are order-fixed)."""
+    import numpy as np
+
+    out = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        r = _bench("--gpus", "1", "--steps", "6", "--warmup", "3", "--dump-outputs", str(d), *extra)
+        assert r["steps"] == 6 and r["ms_per_step"] > 0
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert set(arrs) == {"variables", "gradients", "loss_sum", "correct", "global_step"}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["variables"].size == arrs["gradients"].size >= 3274634  # every parameter of the CNN
+        assert int(arrs["global_step"][0]) == r["config"]["prewarm"]["steps"] + 3 + 6
+        assert abs(float(arrs["loss_sum"][0]) / 1024 - r["config"]["last_loss"]) < 1e-3
+        assert np.abs(arrs["gradients"]).max() > 0
+        out.append(arrs)
+    for k in out[0]:
+        assert np.array_equal(out[0][k], out[1][k]), k
+
+
 def test_bench_single_rank_json_contract():
     r = _bench("--steps", "10", "--warmup", "3")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
