@@ -408,14 +408,12 @@ void ps_service_add_group(int64_t h, int64_t kind, Tensor p, const c10::optional
   a.beta_pow = (beta_pow.has_value() && beta_pow->defined()) ? beta_pow->data_ptr<float>() : nullptr;
   a.global_step = (global_step.has_value() && global_step->defined()) ? global_step->data_ptr<int32_t>() : nullptr;
   a.gs_inc = (int)gs_inc;
-  const size_t bs = (size_t)nseg * sizeof(dtfe::OptSeg), off = (bs + 255) / 256 * 256;
-  a.segs = reinterpret_cast<const dtfe::OptSeg*>(blob.data_ptr());
-  a.work = reinterpret_cast<const dtfe::OptWork*>((const char*)blob.data_ptr() + off);
+  dtfe::opt_blob_plan(blob.data_ptr(), (size_t)nseg, a);
   a.nwork = (int)nwork;
   g.g16 = g16;
   g.hsegs.resize((size_t)nseg);
   g.hwork.resize((size_t)nwork);
-  if (nseg) hchk(hipMemcpy(g.hsegs.data(), a.segs, bs, hipMemcpyDeviceToHost), "plan segs D2H");
+  if (nseg) hchk(hipMemcpy(g.hsegs.data(), a.segs, (size_t)nseg * sizeof(dtfe::OptSeg), hipMemcpyDeviceToHost), "plan segs D2H");
   if (nwork) hchk(hipMemcpy(g.hwork.data(), a.work, (size_t)nwork * sizeof(dtfe::OptWork), hipMemcpyDeviceToHost), "plan work D2H");
   s->groups.push_back(g);
 }
@@ -487,7 +485,7 @@ const SubPlan& sub_plan_of(Service* s, const Group& g, const std::vector<dtfe::O
   }
   SubPlan p;
   p.nwork = (int)wk.size();
-  const size_t bs = segs.size() * sizeof(dtfe::OptSeg), off = (bs + 255) / 256 * 256;
+  const size_t bs = segs.size() * sizeof(dtfe::OptSeg), off = dtfe::opt_blob_work_offset(segs.size());
   std::vector<uint8_t> host(off + wk.size() * sizeof(dtfe::OptWork) + 16, 0);
   if (bs) std::memcpy(host.data(), segs.data(), bs);
   if (!wk.empty()) std::memcpy(host.data() + off, wk.data(), wk.size() * sizeof(dtfe::OptWork));
@@ -510,9 +508,7 @@ dtfe::OptArgs range_args(Service* s, WorkerCh& c, size_t gi, long lo, long hi) {
     a.g = reinterpret_cast<const float*>(c.mailbox);
     a.g16 = nullptr;
   }
-  const size_t bs = g.hsegs.size() * sizeof(dtfe::OptSeg), off = (bs + 255) / 256 * 256;
-  a.segs = reinterpret_cast<const dtfe::OptSeg*>(p.blob.data_ptr());
-  a.work = reinterpret_cast<const dtfe::OptWork*>((const char*)p.blob.data_ptr() + off);
+  dtfe::opt_blob_plan(p.blob.data_ptr(), g.hsegs.size(), a);
   a.nwork = p.nwork;
   a.gscale = 1.f;
   a.skip_advance = 1;
@@ -570,9 +566,7 @@ void launch_apply_range(Service* s, WorkerCh& c, hipStream_t st, long lo, long h
       a.g = reinterpret_cast<const float*>(c.mailbox);
       a.g16 = nullptr;
     }
-    const size_t bs = g.hsegs.size() * sizeof(dtfe::OptSeg), off = (bs + 255) / 256 * 256;
-    a.segs = reinterpret_cast<const dtfe::OptSeg*>(p.blob.data_ptr());
-    a.work = reinterpret_cast<const dtfe::OptWork*>((const char*)p.blob.data_ptr() + off);
+    dtfe::opt_blob_plan(p.blob.data_ptr(), g.hsegs.size(), a);
     a.nwork = p.nwork;
     a.gscale = 1.f;
     a.skip_advance = 1;

@@ -334,11 +334,14 @@ void conv1_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t se
   TORCH_CHECK(dtfe::launch_conv1_copies_fwd(a, cur_stream()), "conv1_gather_fwd: needs B >= 256");
 }
 
-void imgwgrad(const Tensor& src, const optional<Tensor>& dy, const optional<Tensor>& dy_pooled,
-              const optional<Tensor>& dy_argmax, const Tensor& dw, const optional<Tensor>& db, int64_t B, int64_t SH,
-              int64_t SW, int64_t CS, int64_t OH, int64_t OW, int64_t N, int64_t KH, int64_t KW, int64_t stride,
-              int64_t pad, double scale, const optional<Tensor>& ws, int64_t max_blocks,
-              const optional<at::TensorList>& bn_src, double bn_eps, bool defer) {
+// defer: the persistent kernel leaves its partial-slab reduce to a later wgrad_reduce_group and the call
+// returns that reduce's descriptor [nblk, plen, MT, CTW, KC, N]; empty: the reduce (if any) already ran
+std::vector<int64_t> imgwgrad(const Tensor& src, const optional<Tensor>& dy, const optional<Tensor>& dy_pooled,
+                              const optional<Tensor>& dy_argmax, const Tensor& dw, const optional<Tensor>& db,
+                              int64_t B, int64_t SH, int64_t SW, int64_t CS, int64_t OH, int64_t OW, int64_t N,
+                              int64_t KH, int64_t KW, int64_t stride, int64_t pad, double scale,
+                              const optional<Tensor>& ws, int64_t max_blocks, const optional<at::TensorList>& bn_src,
+                              double bn_eps, bool defer) {
   check_cuda(src, "src");
   dtfe::ImgWgradArgs a{};
   a.defer_reduce = defer ? 1 : 0;
@@ -360,7 +363,35 @@ void imgwgrad(const Tensor& src, const optional<Tensor>& dy, const optional<Tens
   a.dw = dw.data_ptr<float>();
   a.db = ptr_or_null<float>(db);
   a.scale = (float)scale;
-  dtfe::launch_imgwgrad(a, cur_stream());
+  dtfe::WpReduceItem r;
+  dtfe::launch_imgwgrad(a, cur_stream(), r);
+  if (r.nblk == 0) return {};
+  return {r.nblk, r.plen, r.MT, r.CTW, r.KC, r.N};
+}
+
+// the reduces that imgwgrad(defer=True) calls left out (desc: their six ints each, in order; every item
+// its own workspace) as ONE grouped launch on the current stream
+void wgrad_reduce_group(at::TensorList ws, at::TensorList dw, const c10::List<optional<Tensor>>& db,
+                        at::ArrayRef<double> scale, at::IntArrayRef desc) {
+  const size_t n = ws.size();
+  TORCH_CHECK(n <= (size_t)dtfe::WP_GROUP_MAX, "wgrad_reduce_group: at most ", dtfe::WP_GROUP_MAX, " reduces");
+  TORCH_CHECK(dw.size() == n && db.size() == n && scale.size() == n && desc.size() == 6 * n,
+              "wgrad_reduce_group: one entry per reduce in every list");
+  dtfe::WpReduceItem it[dtfe::WP_GROUP_MAX];
+  for (size_t i = 0; i < n; ++i) {
+    const int64_t* d = desc.data() + 6 * i;
+    const optional<Tensor> b = db.get(i);
+    check_cuda(ws[i], "ws");
+    check_cuda(dw[i], "dw");
+    TORCH_CHECK(ws[i].scalar_type() == at::kFloat && dw[i].scalar_type() == at::kFloat && d[0] > 0 && d[1] > 0 &&
+                    ws[i].numel() >= d[0] * d[1] && dw[i].numel() == d[5] * d[4],
+                "wgrad_reduce_group: fp32 ws [>= nblk * plen] and dw [N * KC]");
+    TORCH_CHECK(!b || (b->is_cuda() && b->scalar_type() == at::kFloat && b->numel() >= d[5]),
+                "wgrad_reduce_group: fp32 db [N]");
+    it[i] = dtfe::WpReduceItem{ws[i].data_ptr<float>(), dw[i].data_ptr<float>(), ptr_or_null<float>(b), (float)scale[i],
+                               (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5]};
+  }
+  dtfe::launch_wgrad_reduce_group(it, (int)n, cur_stream());
 }
 
 void conv_wgrad(const Tensor& dz, const Tensor& x, const Tensor& dw, const optional<Tensor>& db, int64_t B, int64_t H,
@@ -540,39 +571,26 @@ Tensor opt_pack(const Tensor& segs, const Tensor& work, const Tensor& device_lik
     vw[i].start = w[i * 7 + 5]; vw[i].count = w[i * 7 + 6];
   }
   const size_t bs = ns * sizeof(dtfe::OptSeg), bw = nw * sizeof(dtfe::OptWork);
-  const size_t off_w = (bs + 255) / 256 * 256;
+  const size_t off_w = dtfe::opt_blob_work_offset(ns);
   Tensor host = at::empty({(int64_t)(off_w + bw)}, at::TensorOptions().dtype(at::kByte));
   std::memcpy(host.data_ptr(), vs.data(), bs);
   std::memcpy((char*)host.data_ptr() + off_w, vw.data(), bw);
   return host.to(device_like.device());
 }
 
-// apply_wait_next(done, seen, segs): the NEXT apply_gradients call's items of the segments in the bit mask
-// `segs` wait on the device-side counter pair (OptArgs::wait_done / wait_seen) - a gradient produced on
-// another stream with no graph edge to the optimizer launch (the CNN's conv2 weight-gradient branch)
-struct ApplyWait { int* done = nullptr; int* seen = nullptr; uint32_t segs = 0; };
-thread_local ApplyWait g_apply_wait;
-void apply_wait_next(const Tensor& done, const Tensor& seen, int64_t segs) {
-  check_cuda(done, "done");
-  TORCH_CHECK(done.scalar_type() == at::kInt && seen.scalar_type() == at::kInt && done.numel() >= 1 && seen.numel() >= 1,
-              "apply_wait_next: int32 counters");
-  g_apply_wait = ApplyWait{done.data_ptr<int>(), seen.data_ptr<int>(), (uint32_t)segs};
-}
 void epoch_signal(const Tensor& ctr) {
   check_cuda(ctr, "ctr");
   TORCH_CHECK(ctr.scalar_type() == at::kInt && ctr.numel() >= 1, "epoch_signal: int32 counter");
   dtfe::launch_epoch_signal(ctr.data_ptr<int>(), cur_stream());
 }
 
-void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
-                     double gscale, const optional<Tensor>& s1, const optional<Tensor>& s2, double lr, double beta1,
-                     double beta2, double eps, double momentum, double rho, const optional<Tensor>& beta_pow,
-                     const optional<Tensor>& global_step, int64_t gs_inc, const Tensor& done, const Tensor& blob,
-                     int64_t nseg, int64_t nwork, int64_t group) {
+// the launch arguments of one optimizer (hyper: lr, beta1, beta2, eps, momentum, rho), shared by the
+// single and the grouped op
+dtfe::OptArgs opt_args(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
+                       double gscale, const optional<Tensor>& s1, const optional<Tensor>& s2, const double* hyper,
+                       const optional<Tensor>& beta_pow, const optional<Tensor>& global_step, int64_t gs_inc,
+                       const Tensor& done, const Tensor& blob, int64_t nseg, int64_t nwork) {
   check_cuda(p, "p");
-  // group: 0 = launch now; 1 = queue these args; 2 = queue and launch every queued optimizer in
-  // ONE grouped launch (same kind, disjoint var lists: e.g. the GAN's two Adams)
-  thread_local std::vector<dtfe::OptArgs> pending;
   dtfe::OptArgs a{};
   a.kind = (int)kind;
   a.p = p.data_ptr<float>();
@@ -581,33 +599,65 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
   TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "apply_gradients: exactly one of g / g16");
   a.gscale = (float)gscale;
   a.s1 = ptr_or_null<float>(s1); a.s2 = ptr_or_null<float>(s2);
-  a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
-  a.momentum = (float)momentum; a.rho = (float)rho;
+  a.lr = (float)hyper[0]; a.beta1 = (float)hyper[1]; a.beta2 = (float)hyper[2]; a.eps = (float)hyper[3];
+  a.momentum = (float)hyper[4]; a.rho = (float)hyper[5];
   a.beta_pow = ptr_or_null<float>(beta_pow);
   a.global_step = ptr_or_null<int32_t>(global_step);
   a.gs_inc = (int)gs_inc;
   a.done_counter = reinterpret_cast<uint32_t*>(done.data_ptr());
-  const size_t bs = nseg * sizeof(dtfe::OptSeg);
-  const size_t off_w = (bs + 255) / 256 * 256;
-  a.segs = reinterpret_cast<const dtfe::OptSeg*>(blob.data_ptr());
-  a.work = reinterpret_cast<const dtfe::OptWork*>((const char*)blob.data_ptr() + off_w);
+  dtfe::opt_blob_plan(blob.data_ptr(), (size_t)nseg, a);
   a.nwork = (int)nwork;
   if (kind == dtfe::OPT_ADAM) TORCH_CHECK(a.beta_pow && a.s1 && a.s2, "adam needs slots and beta powers");
   if (kind == dtfe::OPT_RMSPROP) TORCH_CHECK(a.s1 && a.s2, "rmsprop needs slots");
   if (kind == dtfe::OPT_MOMENTUM) TORCH_CHECK(a.s1, "momentum needs a slot");
-  a.wait_done = g_apply_wait.done; a.wait_seen = g_apply_wait.seen; a.wait_segs = g_apply_wait.segs;
-  g_apply_wait = ApplyWait{};
-  if (group == 0) {
-    TORCH_CHECK(pending.empty(), "apply_gradients: a queued group was never launched");
-    dtfe::launch_apply_gradients(a, cur_stream());
-    return;
+  return a;
+}
+
+// wait_done / wait_seen / wait_segs: this launch's items of the segments in the bit mask wait on the
+// device-side counter pair (OptArgs::wait_done / wait_seen) - a gradient produced on another stream with
+// no graph edge to the optimizer launch (the CNN's conv2 weight-gradient branch)
+void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
+                     double gscale, const optional<Tensor>& s1, const optional<Tensor>& s2, double lr, double beta1,
+                     double beta2, double eps, double momentum, double rho, const optional<Tensor>& beta_pow,
+                     const optional<Tensor>& global_step, int64_t gs_inc, const Tensor& done, const Tensor& blob,
+                     int64_t nseg, int64_t nwork, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
+                     int64_t wait_segs) {
+  const double hyper[6] = {lr, beta1, beta2, eps, momentum, rho};
+  dtfe::OptArgs a = opt_args(kind, p, g, g16, gscale, s1, s2, hyper, beta_pow, global_step, gs_inc, done, blob, nseg,
+                             nwork);
+  const bool waits = wait_done.has_value() && wait_done->defined();
+  TORCH_CHECK(waits == (wait_seen.has_value() && wait_seen->defined()) && (waits || wait_segs == 0),
+              "apply_gradients: wait_done, wait_seen and wait_segs go together");
+  if (waits) {
+    check_cuda(*wait_done, "wait_done");
+    check_cuda(*wait_seen, "wait_seen");
+    TORCH_CHECK(wait_done->scalar_type() == at::kInt && wait_seen->scalar_type() == at::kInt &&
+                    wait_done->numel() >= 1 && wait_seen->numel() >= 1 && wait_segs >= 0 && wait_segs >> 32 == 0,
+                "apply_gradients: int32 wait counters and a 32-bit segment mask");
+    a.wait_done = wait_done->data_ptr<int>(); a.wait_seen = wait_seen->data_ptr<int>();
+    a.wait_segs = (uint32_t)wait_segs;
   }
-  pending.push_back(a);
-  if (group == 2) {
-    std::vector<dtfe::OptArgs> q;
-    q.swap(pending);
-    dtfe::launch_apply_gradients_group(q.data(), (int)q.size(), cur_stream());
-  }
+  dtfe::launch_apply_gradients(a, cur_stream());
+}
+
+// 2..OPT_GROUP_MAX optimizers of one kind over disjoint var lists of one parameter buffer (e.g. the GAN's
+// two Adams) in ONE grouped launch; hyper holds six floats per optimizer (lr, beta1, beta2, eps, momentum, rho)
+void apply_gradients_group(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
+                           double gscale, const c10::List<optional<Tensor>>& s1,
+                           const c10::List<optional<Tensor>>& s2, at::ArrayRef<double> hyper,
+                           const c10::List<optional<Tensor>>& beta_pow,
+                           const c10::List<optional<Tensor>>& global_step, at::IntArrayRef gs_inc,
+                           at::TensorList done, at::TensorList blob, at::IntArrayRef nseg, at::IntArrayRef nwork) {
+  const size_t n = done.size();
+  TORCH_CHECK(n >= 1 && n <= (size_t)dtfe::OPT_GROUP_MAX, "apply_gradients_group: 1..4 optimizers");
+  TORCH_CHECK(s1.size() == n && s2.size() == n && hyper.size() == 6 * n && beta_pow.size() == n &&
+                  global_step.size() == n && gs_inc.size() == n && blob.size() == n && nseg.size() == n &&
+                  nwork.size() == n, "apply_gradients_group: one entry per optimizer in every list");
+  dtfe::OptArgs q[dtfe::OPT_GROUP_MAX];
+  for (size_t i = 0; i < n; ++i)
+    q[i] = opt_args(kind, p, g, g16, gscale, s1.get(i), s2.get(i), hyper.data() + 6 * i, beta_pow.get(i),
+                    global_step.get(i), gs_inc[i], done[i], blob[i], nseg[i], nwork[i]);
+  dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
 }
 
 // ---------------------------------------------------------- elementwise
@@ -1218,10 +1268,8 @@ TORCH_LIBRARY(dtfe, m) {
   m.def(
       "imgwgrad(Tensor src, Tensor? dy, Tensor? dy_pooled, Tensor? dy_argmax, Tensor(a!) dw, Tensor(b!)? db, int B,"
       " int SH, int SW, int CS, int OH, int OW, int N, int KH, int KW, int stride, int pad, float scale, Tensor(c!)? ws=None,"
-      " int max_blocks=0, Tensor[]? bn_src=None, float bn_eps=0.001, bool defer=False) -> ()");
-  m.def("wgrad_flush() -> int");
-  m.def("wgrad_pending() -> int");
-  m.def("wgrad_discard() -> int");
+      " int max_blocks=0, Tensor[]? bn_src=None, float bn_eps=0.001, bool defer=False) -> int[]");
+  m.def("wgrad_reduce_group(Tensor[] ws, Tensor(a!)[] dw, Tensor?[] db, float[] scale, int[] desc) -> ()");
   m.def(
       "conv_wgrad(Tensor dz, Tensor x, Tensor(a!) dw, Tensor(b!)? db, int B, int H, int W, int C, int Cout, int OH,"
       " int OW, int KH, int KW, int stride, int pad, float scale) -> ()");
@@ -1236,7 +1284,12 @@ TORCH_LIBRARY(dtfe, m) {
   m.def(
       "apply_gradients(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor(b!)? s1, Tensor(c!)? s2,"
       " float lr, float beta1, float beta2, float eps, float momentum, float rho, Tensor(d!)? beta_pow,"
-      " Tensor(e!)? global_step, int gs_inc, Tensor(f!) done, Tensor blob, int nseg, int nwork, int group=0) -> ()");
+      " Tensor(e!)? global_step, int gs_inc, Tensor(f!) done, Tensor blob, int nseg, int nwork,"
+      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0) -> ()");
+  m.def(
+      "apply_gradients_group(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor?[] s1, Tensor?[] s2,"
+      " float[] hyper, Tensor?[] beta_pow, Tensor?[] global_step, int[] gs_inc, Tensor[] done, Tensor[] blob,"
+      " int[] nseg, int[] nwork) -> ()");
   m.def("wgrad_tallk(Tensor A, int lda, Tensor B, int ldb, int M, int N, int K, Tensor(a!) out, int ldc,"
         " Tensor(b!)? bias, Tensor(c!) ws, int splits, float scale) -> ()");
   m.def("seq_stage(Tensor x, Tensor(a!) xh, int T, int I, Tensor ysrc, Tensor(b!) ydst, Tensor(c!)[] zero) -> ()");
@@ -1256,7 +1309,6 @@ TORCH_LIBRARY(dtfe, m) {
         " Tensor(d!) gw, Tensor(e!)? gb, Tensor(f!) dd1, Tensor(g!) ddf, Tensor(h!) gen_loss, Tensor(i!) disc_loss,"
         " Tensor(j!) ws, float clamp_eps=0.0) -> bool");
   m.def("gan_head_ws_floats(int B, int DH) -> int");
-  m.def("apply_wait_next(Tensor done, Tensor seen, int segs) -> ()");
   m.def("epoch_signal(Tensor(a!) ctr) -> ()");
   m.def("mse_sigmoid(Tensor y, Tensor t, Tensor(a!) loss, Tensor(b!) dz, Tensor(c!)? ws=None) -> ()");
   m.def("colsum(Tensor x, int M, int N, int ld, Tensor(a!) db, float scale) -> ()");
@@ -1294,6 +1346,7 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("head_wgrad", &head_wgrad);
   m.impl("gemm_group", &gemm_group);
   m.impl("apply_gradients", &apply_gradients);
+  m.impl("apply_gradients_group", &apply_gradients_group);
   m.impl("gather_rows", &gather_rows);
   m.impl("seq_stage", &seq_stage);
   m.impl("wgrad_tallk", &wgrad_tallk);
@@ -1303,7 +1356,6 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("gan_loss", &gan_loss);
   m.impl("mse_sigmoid", &mse_sigmoid);
   m.impl("gan_disc_head", &gan_disc_head);
-  m.impl("apply_wait_next", &apply_wait_next);
   m.impl("epoch_signal", &epoch_signal);
   m.impl("colsum", &colsum);
   m.impl("unpool_f32", &unpool_f32);
@@ -1315,19 +1367,12 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("imgconv", &imgconv);
   m.impl("dense_head", &dense_head);
   m.impl("imgwgrad", &imgwgrad);
+  m.impl("wgrad_reduce_group", &wgrad_reduce_group);
   m.impl("lstm_cell_fwd", &lstm_cell_fwd);
   m.impl("lstm_cell_bwd", &lstm_cell_bwd);
 }
 
-// every weight-gradient reduce queued with imgwgrad(defer=True), as one grouped launch on the current stream
-int64_t wgrad_flush() { return dtfe::flush_wgrad_reduces(cur_stream()); }
-int64_t wgrad_pending() { return dtfe::pending_wgrad_reduces(); }
-int64_t wgrad_discard() { return dtfe::discard_wgrad_reduces(); }
-
 TORCH_LIBRARY_IMPL(dtfe, CompositeExplicitAutograd, m) {
   m.impl("opt_pack", &opt_pack);
-  m.impl("wgrad_flush", &wgrad_flush);
-  m.impl("wgrad_pending", &wgrad_pending);
-  m.impl("wgrad_discard", &wgrad_discard);
   m.impl("gan_head_ws_floats", &gan_head_ws_floats);
 }

@@ -83,18 +83,20 @@ struct ImgWgradArgs {
   int max_blocks;
   int diag;                 // ablation bits for kernel experiments (DTFE_DIAG iw=<bits>; 0 in production)
   BnSrc bns;                // BatchNorm + ReLU of src formed while staging it (persistent kernel; see ImgConvArgs)
-  // persistent kernel with a workspace: queue the partial-slab reduce instead of launching it;
-  // flush_wgrad_reduces launches every queued one together (the caller's workspaces must differ)
+  // persistent kernel with a workspace: leave the partial-slab reduce to the caller instead of
+  // launching it; launch_imgwgrad hands back what that reduce needs (WpReduceItem)
   int defer_reduce;
 };
 
-// launch every deferred weight-gradient reduce (ImgWgradArgs::defer_reduce) as ONE grouped launch on s;
-// returns how many there were
-int flush_wgrad_reduces(hipStream_t s);
-// queued-but-unflushed deferred reduces of this thread, and dropping them (a backward that was
-// interrupted between an imgwgrad(defer=True) and its flush leaves them behind)
-int pending_wgrad_reduces();
-int discard_wgrad_reduces();
+// One weight-gradient partial-slab reduce: dw / db += scale * the sum of the nblk slabs (plen floats
+// each, the persistent kernel's MT x CTW register layout) in ws.  nblk == 0: nothing to reduce
+struct WpReduceItem {
+  const float* ws; float* dw; float* db; float scale; int nblk, plen, MT, CTW, KC, N;
+};
+constexpr int WP_GROUP_MAX = 32;
+// n (<= WP_GROUP_MAX) deferred reduces, each with its own workspace, as ONE grouped launch on s:
+// every item is summed exactly as its own reduce launch would (n == 0: no launch)
+void launch_wgrad_reduce_group(const WpReduceItem* it, int n, hipStream_t s);
 
 bool imgconv_supported(int SH, int SW, int CS, int N, int KH, int KW, int stride, int pad);
 // returns whether a.sc_src was added by the launch (false: the caller adds the shortcut gradient)
@@ -107,10 +109,12 @@ bool imgwgrad_supported(const ImgWgradArgs& a);
 // floats of the partial-sum workspace the weight-gradient kernels need (256 workgroup slabs);
 // mirrored by ops.wgrad_ws_floats
 long imgwgrad_ws_floats(int N, int KC);
-void launch_imgwgrad(const ImgWgradArgs& a, hipStream_t s);
+// deferred: the reduce that a launch with a.defer_reduce left out; nblk == 0 when there is none
+// (defer_reduce off, a non-persistent kernel, no workspace)
+void launch_imgwgrad(const ImgWgradArgs& a, hipStream_t s, WpReduceItem& deferred);
 // persistent variant (dW accumulated in registers across a workgroup's images);
 // returns false when the shape does not fit it
-bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s);
+bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s, WpReduceItem& deferred);
 // MNIST conv1 (28x28x1, 5x5 SAME, 32 channels, B >= 256): shifted-copy kernels
 // (imgconv1_copies.hip); false when the shape is not that layer
 bool launch_conv1_copies_fwd(const ImgConvArgs& a, hipStream_t s);

@@ -718,8 +718,9 @@ static void launch_wg1(const ImgWgradArgs& a0, hipStream_t s) {
   hipLaunchKernelGGL(k, dim3(groups), dim3(IC_THREADS), lds, s, a);
 }
 
-void launch_imgwgrad(const ImgWgradArgs& a, hipStream_t s) {
+void launch_imgwgrad(const ImgWgradArgs& a, hipStream_t s, WpReduceItem& deferred) {
   if (!imgwgrad_supported(a)) throw std::runtime_error("imgwgrad: shape not supported");
+  deferred = WpReduceItem{};
   if (a.bns.stats && a.CS <= 4) throw std::runtime_error("imgwgrad: BN-on-load needs the persistent kernel");
   if (a.CS <= 4) {
     if (!a.src) throw std::runtime_error("imgwgrad: few-channel path needs src");
@@ -731,7 +732,7 @@ void launch_imgwgrad(const ImgWgradArgs& a, hipStream_t s) {
     }
     return;
   }
-  if (launch_imgwgrad_persistent(a, s)) return;
+  if (launch_imgwgrad_persistent(a, s, deferred)) return;
   if (a.bns.stats) throw std::runtime_error("imgwgrad: BN-on-load needs the persistent kernel (B >= 128)");
   if (a.N <= 16) launch_wg<1, 8>(a, s);
   else if (a.N <= 32) launch_wg<2, 6>(a, s);

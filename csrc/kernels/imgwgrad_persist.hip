@@ -27,7 +27,6 @@
 
 #include <stdexcept>
 #include <type_traits>
-#include <vector>
 
 namespace dtfe {
 
@@ -386,10 +385,6 @@ __global__ __launch_bounds__(256) void wp_reduce_kernel(const float* __restrict_
 
 // Several deferred weight-gradient reduces (each its own workspace) in ONE launch: workgroup
 // ranges [first[i], first[i + 1]) reduce item i, exactly as its own wp_reduce_kernel launch would
-struct WpReduceItem {
-  const float* ws; float* dw; float* db; float scale; int nblk, plen, MT, CTW, KC, N;
-};
-constexpr int WP_GROUP_MAX = 32;
 struct WpReduceGroup {
   WpReduceItem it[WP_GROUP_MAX];
   int first[WP_GROUP_MAX + 1];
@@ -402,8 +397,6 @@ __global__ __launch_bounds__(256) void wp_reduce_group_kernel(WpReduceGroup g) {
   const WpReduceItem& t = g.it[i];
   wp_reduce_body(t.ws, t.nblk, t.plen, t.MT, t.CTW, t.KC, t.N, t.dw, t.db, t.scale, blockIdx.x - g.first[i], red);
 }
-
-thread_local std::vector<WpReduceItem> g_wp_deferred;  // queued by deferred launches, flushed together
 
 }  // namespace
 
@@ -469,7 +462,7 @@ WPGeom wp_geom(const ImgWgradArgs& a) {
 size_t wp_lds(const WPGeom& G) { return ((size_t)G.img_off + (size_t)G.nk * 32 * G.NPS) * sizeof(bf16); }
 
 template <int MT, int CTW, bool POOLED, int KG = 1, bool BNX = false>
-bool wp_launch(const ImgWgradArgs& a, const WPGeom& G, hipStream_t s) {
+bool wp_launch(const ImgWgradArgs& a, const WPGeom& G, hipStream_t s, WpReduceItem& deferred) {
   size_t lds = wp_lds(G);
   if (lds > 150 * 1024) return false;
   if ((G.ctiles + CTW - 1) / CTW > 8 / KG) return false;
@@ -497,8 +490,7 @@ bool wp_launch(const ImgWgradArgs& a, const WPGeom& G, hipStream_t s) {
     if (a.ws) {
       const int plen = wp_part_len(MT, CTW, a.N), KC = a.KH * a.KW * a.CS;
       if (a.defer_reduce) {
-        if (g_wp_deferred.size() >= (size_t)WP_GROUP_MAX) throw std::runtime_error("imgwgrad: too many deferred reduces");
-        g_wp_deferred.push_back(WpReduceItem{a.ws, a.dw, a.db, a.scale, grid, plen, MT, CTW, KC, a.N});
+        deferred = WpReduceItem{a.ws, a.dw, a.db, a.scale, grid, plen, MT, CTW, KC, a.N};
       } else {
         hipLaunchKernelGGL(wp_reduce_kernel, dim3((plen / 4 + 15) / 16), dim3(256), 0, s, a.ws, grid, plen, MT, CTW,
                            KC, a.N, a.dw, a.db, a.scale);
@@ -524,27 +516,21 @@ bool wp_launch(const ImgWgradArgs& a, const WPGeom& G, hipStream_t s) {
 
 }  // namespace
 
-int flush_wgrad_reduces(hipStream_t s) {
-  const int n = (int)g_wp_deferred.size();
-  if (n == 0) return 0;
+void launch_wgrad_reduce_group(const WpReduceItem* it, int n, hipStream_t s) {
+  if (n == 0) return;
+  if (n < 0 || n > WP_GROUP_MAX) throw std::runtime_error("wgrad_reduce_group: too many deferred reduces");
   WpReduceGroup g{};
   g.n = n;
   g.first[0] = 0;
   for (int i = 0; i < n; ++i) {
-    g.it[i] = g_wp_deferred[i];
-    g.first[i + 1] = g.first[i] + (g.it[i].plen / 4 + 15) / 16;
+    const WpReduceItem& t = it[i];
+    if (t.nblk < 1 || t.nblk > 256 || t.MT < 1 || t.CTW < 1 || t.N < 1 || t.KC < 1 ||
+        t.plen != wp_part_len(t.MT, t.CTW, t.N))
+      throw std::runtime_error("wgrad_reduce_group: not a descriptor of a deferred imgwgrad");
+    g.it[i] = t;
+    g.first[i + 1] = g.first[i] + (t.plen / 4 + 15) / 16;
   }
-  g_wp_deferred.clear();
   hipLaunchKernelGGL(wp_reduce_group_kernel, dim3(g.first[n]), dim3(256), 0, s, g);
-  return n;
-}
-
-int pending_wgrad_reduces() { return (int)g_wp_deferred.size(); }
-
-int discard_wgrad_reduces() {
-  const int n = (int)g_wp_deferred.size();
-  g_wp_deferred.clear();
-  return n;
 }
 
 long imgwgrad_ws_floats(int N, int KC) {
@@ -554,7 +540,7 @@ long imgwgrad_ws_floats(int N, int KC) {
   return 256L * (plain > reg ? plain : reg);
 }
 
-bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s) {
+bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s, WpReduceItem& deferred) {
   if (a.CS % 16 || a.N % 8 || a.N > 64 || a.OW > 32 || a.B < 128) return false;
   const bool pooled = a.dy == nullptr;
   if (pooled && ((a.OH | a.OW) & 1)) return false;
@@ -566,19 +552,19 @@ bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s) {
   // (BN + ReLU of the source on staging: compile-time instances of the ResNet configurations only)
   const bool bn = a.bns.stats != nullptr;
   if (ks && G.ctiles <= 9 && a.N <= 16 && !pooled)
-    return bn ? wp_launch<1, 9, false, 8, true>(a, G, s) : wp_launch<1, 9, false, 8>(a, G, s);
+    return bn ? wp_launch<1, 9, false, 8, true>(a, G, s, deferred) : wp_launch<1, 9, false, 8>(a, G, s, deferred);
   if (ks && G.ctiles <= 9 && a.N <= 32 && !pooled)
-    return bn ? wp_launch<2, 9, false, 8, true>(a, G, s) : wp_launch<2, 9, false, 8>(a, G, s);
+    return bn ? wp_launch<2, 9, false, 8, true>(a, G, s, deferred) : wp_launch<2, 9, false, 8>(a, G, s, deferred);
   if (ks && G.ctiles <= 18 && a.N <= 32 && !pooled)
-    return bn ? wp_launch<2, 9, false, 4, true>(a, G, s) : wp_launch<2, 9, false, 4>(a, G, s);
+    return bn ? wp_launch<2, 9, false, 4, true>(a, G, s, deferred) : wp_launch<2, 9, false, 4>(a, G, s, deferred);
   if (a.N > 32 && ks && G.ctiles <= 40 && !pooled)
-    return bn ? wp_launch<4, 5, false, 1, true>(a, G, s) : wp_launch<4, 5, false>(a, G, s);
+    return bn ? wp_launch<4, 5, false, 1, true>(a, G, s, deferred) : wp_launch<4, 5, false>(a, G, s, deferred);
   if (bn) return false;
   if (a.N > 32) {
-    if (ctw <= 7) return pooled ? wp_launch<4, 7, true>(a, G, s) : wp_launch<4, 7, false>(a, G, s);
+    if (ctw <= 7) return pooled ? wp_launch<4, 7, true>(a, G, s, deferred) : wp_launch<4, 7, false>(a, G, s, deferred);
     return false;
   }
-  if (ctw <= 8) return pooled ? wp_launch<2, 8, true>(a, G, s) : wp_launch<2, 8, false>(a, G, s);
+  if (ctw <= 8) return pooled ? wp_launch<2, 8, true>(a, G, s, deferred) : wp_launch<2, 8, false>(a, G, s, deferred);
   return false;
 }
 

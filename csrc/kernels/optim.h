@@ -30,6 +30,9 @@ struct OptWork {
   long start, count;
 };
 
+// An optimizer plan is one device blob: nseg OptSeg, then the OptWork items at the next 256-B boundary
+inline size_t opt_blob_work_offset(size_t nseg) { return (nseg * sizeof(OptSeg) + 255) / 256 * 256; }
+
 struct OptArgs {
   int kind;
   float* p;
@@ -54,6 +57,11 @@ struct OptArgs {
   // epoch_signal_kernel after the producer); the last workgroup then advances *wait_seen
   const int* wait_done; int* wait_seen; uint32_t wait_segs;
 };
+// points a.segs / a.work into a plan blob of nseg segments
+inline void opt_blob_plan(const void* blob, size_t nseg, OptArgs& a) {
+  a.segs = reinterpret_cast<const OptSeg*>(blob);
+  a.work = reinterpret_cast<const OptWork*>(static_cast<const char*>(blob) + opt_blob_work_offset(nseg));
+}
 // *ctr += 1 (agent-scope release) - launched on the producer's stream right after the producer
 void launch_epoch_signal(int* ctr, hipStream_t s);
 

@@ -257,7 +257,7 @@ class MnistCnnTrainer:
             self.c2_done = torch.zeros(1, device=d, dtype=torch.int32)
             self.c2_seen = torch.zeros(1, device=d, dtype=torch.int32)
         self.defer_join = False
-        self._signalled = False
+        self._pending_join = False
         # (the conv weight-gradient partial reduces stay their own launches: summing the partial slabs
         # inside the Adam launch measured 0.2033-0.2042 vs 0.1989-0.1997 ms/step,
         # profiles/r4_cnn_step_b1024.txt)
@@ -303,6 +303,9 @@ class MnistCnnTrainer:
                       parts=self.head_parts)
 
     def forward_backward(self):
+        """Forward and backward (+ all-reduce and the split Adam of a data-parallel step).  Returns whether
+        the conv2 weight-gradient branch signalled ``c2_done`` instead of rejoining the launch stream
+        (``defer_join``): the caller's optimizer launch must then wait on it (``step``)."""
         B = self.B
         K1 = 7 * 7 * C2
         self.schedule = []
@@ -335,7 +338,6 @@ class MnistCnnTrainer:
             if signal:
                 ops.epoch_signal(self.c2_done)
         ops.imgwgrad(self.x, self.gw["wc1"], self.gw["bc1"], dy_pooled=self.dp1, dy_argmax=self.a1, **self.ic1)
-        self._signalled = signal
         if signal:
             self._pending_join = True
         elif self.par:
@@ -349,6 +351,7 @@ class MnistCnnTrainer:
             self.allreduce.wait()
         if self._late is not None:
             self.opt_conv.step(grad16=self._late[0], gscale=self._late[1], gs_inc=1)
+        return signal
 
     def _head_wgrad(self):
         """head wgrad: dW[10][1024] = dlogit^T . H, db = sum dlogit (dedicated whole-batch kernel; the
@@ -402,12 +405,10 @@ class MnistCnnTrainer:
         bf16 gradients to apply instead of P.grad; ``gscale`` defaults to 1/world."""
         gscale = 1.0 / self.world if gscale is None else gscale
         if not self.par or not (self.late_split and self.allreduce is not None):
-            self.forward_backward()
-            if getattr(self, "_signalled", False):  # Adam's conv2 items wait for the branch's device-side signal
-                vl = self.opt.var_list
-                mask = sum(1 << vl.index(self.names[k]) for k in ("wc2", "bc2"))
-                ops.apply_wait_next(self.c2_done, self.c2_seen, mask)
-            self.opt.step(grad16=grad16, gscale=gscale)
+            wait = None
+            if self.forward_backward():  # Adam's conv2 items wait for the branch's device-side signal
+                wait = (self.c2_done, self.c2_seen, [self.names["wc2"], self.names["bc2"]])
+            self.opt.step(grad16=grad16, gscale=gscale, wait=wait)
             return
         self._ensure_split()
         self._late = (grad16, gscale)
@@ -419,7 +420,7 @@ class MnistCnnTrainer:
     def join_side(self):
         """Rejoin the conv2 weight-gradient branch to the launch stream (after the last step of a replay when
         ``defer_join`` is on; a no-op otherwise)."""
-        if getattr(self, "_pending_join", False):
+        if self._pending_join:
             torch.cuda.current_stream(self.device).wait_stream(self.s_c2)
             self._pending_join = False
 

@@ -133,6 +133,8 @@ class Conv:
         # the implicit-GEMM data gradient can accumulate into dx (a block's input gradient gets its
         # shortcut share first, then the conv's on top: no separate add pass)
         self.can_accum = not self.img_dgrad and self.cin % 64 == 0 and self.cout % 64 == 0
+        # (workspace, ops.WgradReduces) while the program defers this conv's weight-gradient reduce
+        self.defer = (None, None)
 
     def fwd(self, x, stats=None, bn_src=None):
         """Forward; ``stats``: the following BatchNorm's [2][C] accumulators, filled by the conv
@@ -156,14 +158,14 @@ class Conv:
     def wgrad(self, dy, x, after=None, bn_src=None):
         """``after``: the side stream's fork point (SideStream.fork_point, taken when dy was final).
         ``bn_src``: as in fwd (x is then the BN's raw input)."""
-        dws = getattr(self, "defer_ws", None)
+        dws, reduces = self.defer
         if bn_src is not None:
             assert self.img_wgrad
             ops.imgwgrad(x, self.gw, None, dy=dy, bn_src=bn_src.src_args(), bn_eps=BN_EPS, workspace=dws,
-                         defer=dws is not None, **self.ic)
+                         defer=reduces, **self.ic)
             return
         if dws is not None and self.img_wgrad:
-            ops.imgwgrad(x, self.gw, None, dy=dy, workspace=dws, defer=True, **self.ic)
+            ops.imgwgrad(x, self.gw, None, dy=dy, workspace=dws, defer=reduces, **self.ic)
             return
         side = getattr(self, "side", None)
         if side is not None and not self.img_wgrad and self.cin % 64 == 0 and self.cout % 64 == 0:
@@ -253,7 +255,7 @@ _WGRAD_STREAM = os.environ.get("DTFE_WGRAD_STREAM", "1") != "0"
 _R20_SRC_FOLD = True
 # classifier head forward + backward in one launch (ops.dense_head)
 _HEAD_FUSE = True
-# ResNet-20 weight-gradient reduces deferred to grouped launches (ops.wgrad_flush)
+# ResNet-20 weight-gradient reduces deferred to grouped launches (ops.WgradReduces)
 _WGRAD_DEFER = True
 
 
@@ -730,6 +732,7 @@ class ResNetProgram(StepProgram):
         self._defer_ok = self.device.type == "cuda" and _WGRAD_DEFER and 0 < len(self._defer_convs) <= 32
         self._defer_ws = {c: torch.empty(ops.wgrad_ws_floats(c.cout, c.k * c.k * c.cin), device=dev)
                           for c in self._defer_convs} if self._defer_ok else {}
+        self._reduces = ops.WgradReduces()
         self.defer_wgrad = False
         # ResNet-50 (bottleneck) weight gradients on a side stream (SideStream; DTFE_WGRAD_STREAM=0 off)
         self.side = None
@@ -746,12 +749,12 @@ class ResNetProgram(StepProgram):
         event recorded there, the compute stream does not (no per-block join serialising the
         data-gradient chain behind the weight gradients).
 
-        Deferred weight-gradient reduces: the ones queued so far are flushed as ONE grouped launch
+        Deferred weight-gradient reduces: the ones collected so far are flushed as ONE grouped launch
         just before the hook launches a bucket (only when a bucket boundary is crossed, so the
         multi-rank schedules keep most of the 18 -> 1 saving; profiles/r6_resnet20_bucket_flush.txt)."""
         if self.grad_ready is not None:
             if self.defer_wgrad and self._bucket_completes(lo):
-                ops.wgrad_flush()
+                self._reduces.flush()
             after = None
             if self.side is not None and self.side.pending:
                 after = [self.side.mark()]
@@ -804,32 +807,21 @@ class ResNetProgram(StepProgram):
                          correct=self.correct)
 
     def backward(self):
-        # the deferred weight-gradient queue (a thread-local list of device pointers in the kernel
-        # library) must be empty here: a stale entry would reduce into freed or foreign buffers
-        if self._defer_ok:
-            stale = ops.wgrad_pending()
-            if stale:
-                ops.wgrad_discard()
-                raise RuntimeError(f"ResNetProgram.backward: {stale} deferred weight-gradient reduce(s) left "
-                                   "queued by an earlier interrupted backward or a stray imgwgrad(defer=True); "
-                                   "discarded - rerun the step")
         try:
             self._backward()
-        except BaseException:
-            if self._defer_ok:
-                ops.wgrad_discard()  # nothing queued by this backward may leak into the next one
-            raise
+        finally:
+            self._reduces.clear()  # flushed by a whole backward; what an interrupted one collected is dropped
 
     def _backward(self):
         L, P, B = self.L, self.P, self.batch_size
-        # the whole-image weight gradients queue their partial-slab reduces (own workspaces); ONE
-        # grouped launch sums them: at the end of the backward with one replica
+        # the whole-image weight gradients leave their partial-slab reduces (own workspaces) in the
+        # program's collector; ONE grouped launch sums them: at the end of the backward with one replica
         # (profiles/r5_resnet20_kernels.txt), before each bucket's launch when a progress hook (all-reduce
         # / ps push) waits on per-block gradients (_ready)
         self.defer_wgrad = self._defer_ok
         self._ready_lo = 1 << 62
         for c in self._defer_convs:
-            c.defer_ws = self._defer_ws[c] if self.defer_wgrad else None
+            c.defer = (self._defer_ws[c], self._reduces) if self.defer_wgrad else (None, None)
         d = L["dense"]
         fused = getattr(self, "head_fused", False)
         if not fused:
@@ -862,7 +854,7 @@ class ResNetProgram(StepProgram):
             L["stem_bn"].bwd(dout, st.y, self.dc_stem)
         st.wgrad(self.dc_stem, self.x)
         if self.defer_wgrad:
-            ops.wgrad_flush()  # every (remaining) deferred weight-gradient reduce in one launch
+            self._reduces.flush()  # every (remaining) deferred weight-gradient reduce in one launch
         if self.side is not None:
             self.side.join()
         self._ready(0)

@@ -27,8 +27,8 @@ __all__ = [
     "TILE_DIMS", "FC_TILE", "TILE_SMALL", "GEMM_KTILE", "GLDS_TILES", "glds_ok", "ones_page", "bn_stats", "bn_apply", "bn_bwd_stats",
     "bn_bwd_apply", "relu_bits", "shortcut_grad_add",
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_uniform",
-    "imgconv_shortcut", "dense_head", "wgrad_flush", "wgrad_pending", "wgrad_discard", "conv1_wgrad_pooled_f32",
-    "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "apply_wait_next", "epoch_signal",
+    "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
+    "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -428,28 +428,6 @@ def imgconv_shortcut(w, dx, g, sc_stride, *, src, **geom) -> bool:
 _WG_WS = {}
 
 
-def wgrad_flush() -> int:
-    """Launch every weight-gradient reduce queued by imgwgrad(defer=True) as ONE grouped launch on the
-    current stream (each deferred call needs its own workspace).  CPU: nothing is ever deferred."""
-    if available():
-        return int(require().wgrad_flush())
-    return 0
-
-
-def wgrad_pending() -> int:
-    """Deferred weight-gradient reduces queued on this thread and not yet flushed."""
-    if available():
-        return int(require().wgrad_pending())
-    return 0
-
-
-def wgrad_discard() -> int:
-    """Drop this thread's queued deferred reduces (after an interrupted backward); returns how many."""
-    if available():
-        return int(require().wgrad_discard())
-    return 0
-
-
 def wgrad_ws_floats(N: int, KC: int) -> int:
     """Floats of the weight-gradient partial-sum workspace (256 workgroup slabs) - mirrors
     imgwgrad_ws_floats in csrc/kernels/imgwgrad_persist.hip (the register-layout slabs of the
@@ -471,16 +449,37 @@ def wgrad_workspace(device, numel):
     return ws
 
 
+class WgradReduces(list):
+    """The partial-slab reduces that ``imgwgrad(defer=self)`` calls left out (each call its own
+    workspace), launched together by ``flush``.  It holds the tensors themselves, so nothing a
+    pending reduce points at can be freed underneath it."""
+
+    def add(self, ws, dw, db, scale, desc):
+        self.append((ws, dw, db, float(scale), list(desc)))
+
+    def flush(self) -> int:  # ONE grouped launch on the current stream; returns how many it summed
+        n = len(self)
+        if n:
+            ws, dw, db, scale, desc = (list(v) for v in zip(*self))
+            self.clear()
+            require().wgrad_reduce_group(ws, dw, db, scale, sum(desc, []))
+        return n
+
+
 def imgwgrad(src, dw, db, *, B, SH, SW, CS, OH, OW, N, KH, KW, stride=1, pad=0, dy=None, dy_pooled=None,
-             dy_argmax=None, scale=1.0, workspace=None, max_blocks=0, bn_src=None, bn_eps=1e-3, defer=False):
+             dy_argmax=None, scale=1.0, workspace=None, max_blocks=0, bn_src=None, bn_eps=1e-3, defer=None):
     """dW[n][tap][c] += scale * sum_p dY[p][n] src[p*stride-pad+tap][c]; db += scale * sum dY.
     On the GPU the persistent kernel stores per-workgroup partials in `workspace`
-    (default: a cached per-device buffer) and a second kernel sums them."""
+    (default: a cached per-device buffer) and a second kernel sums them - or, with ``defer`` a
+    WgradReduces (and a workspace of the call's own), that sum joins the collector's next flush."""
     if dw.is_cuda:
         if workspace is None and (CS % 16 == 0 or CS == 1):
             workspace = wgrad_workspace(dw.device, wgrad_ws_floats(N, KH * KW * CS))
-        require().imgwgrad(src, dy, dy_pooled, dy_argmax, dw, db, B, SH, SW, CS, OH, OW, N, KH, KW, stride, pad,
-                           scale, workspace, max_blocks, bn_src=bn_src, bn_eps=bn_eps, defer=defer)
+        deferred = defer is not None and defer is not False
+        desc = require().imgwgrad(src, dy, dy_pooled, dy_argmax, dw, db, B, SH, SW, CS, OH, OW, N, KH, KW, stride,
+                                  pad, scale, workspace, max_blocks, bn_src=bn_src, bn_eps=bn_eps, defer=deferred)
+        if desc:  # (empty: the kernel that ran had no reduce to leave out)
+            defer.add(workspace, dw, db, scale, desc)
         return
     if bn_src is not None:  # the source's BN + ReLU (nothing saved: the forward did)
         src = _bn_src_ref(src, bn_src, bn_eps, 0.99, False)
@@ -681,10 +680,12 @@ def opt_pack(segs, work, device_like):
 
 
 def apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
-                    gs_inc, done, blob, nseg, nwork, group=0):
-    """group: 0 launch now, 1 queue, 2 queue + launch all queued optimizers as one grouped launch."""
+                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0):
+    """The launch's items of the var-list segments in bit mask ``wait_segs`` wait (on the device) until
+    ``wait_done`` exceeds ``wait_seen`` - a gradient produced on another stream that signals with
+    epoch_signal(wait_done) instead of a stream join; the launch's last workgroup advances ``wait_seen``."""
     require().apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow,
-                              global_step, gs_inc, done, blob, nseg, nwork, group)
+                              global_step, gs_inc, done, blob, nseg, nwork, wait_done, wait_seen, wait_segs)
 
 
 # ------------------------------------------------------------- elementwise
@@ -810,15 +811,8 @@ def gan_loss(d_real, d_fake, gen_loss, disc_loss, dz_real_disc, dz_fake_disc, dz
     dz_fake_gen.view(-1).copy_(-(1 - pf) / B)
 
 
-def apply_wait_next(done, seen, segs: int):
-    """The next apply_gradients launch's items of the var-list segments in bit mask ``segs`` wait (on the
-    device) until ``done`` exceeds ``seen`` - a gradient produced on another stream that signals with
-    epoch_signal(done) instead of a stream join; the launch's last workgroup advances ``seen``."""
-    require().apply_wait_next(done, seen, int(segs))
-
-
 def epoch_signal(ctr):
-    """ctr += 1 on the current stream (after the producer a later apply_wait_next consumer waits for)."""
+    """ctr += 1 on the current stream (after the producer that a later apply_gradients(wait_done=ctr) waits for)."""
     require().epoch_signal(ctr)
 
 

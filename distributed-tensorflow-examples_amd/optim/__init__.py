@@ -234,16 +234,28 @@ class Optimizer:
         self._blob = ops.opt_pack(torch.tensor(segs, dtype=torch.int64), torch.tensor(work, dtype=torch.int64),
                                   self.P.master)
 
-    def step(self, grad=None, grad16=None, gscale: float = 1.0, gs_inc: int = 1, group: int = 0):
-        """Apply gradients (default: the FlatParams grad buffer) to var_list.  ``group`` (GPU):
-        1 queues this apply, 2 queues it and launches every queued one together (``step_all``)."""
+    def _wait_mask(self, names) -> int:  # the kernel's wait_segs: 32 bits of var_list indices
+        idx = [self.var_list.index(n) if n in self.var_list else -1 for n in names]
+        if any(not 0 <= i < 32 for i in idx):
+            raise ValueError(f"Optimizer.step(wait=...): {list(names)} must be among the first 32 of var_list")
+        return sum(1 << i for i in idx)
+
+    def _hyper(self):
         c = self.cfg
+        return [c.lr, c.beta1, c.beta2, c.resolved_eps(), c.momentum, c.rho]
+
+    def step(self, grad=None, grad16=None, gscale: float = 1.0, gs_inc: int = 1, wait=None):
+        """Apply gradients (default: the FlatParams grad buffer) to var_list.  ``wait`` (GPU; ignored
+        on the CPU) = ``(done, seen, var_names)``: the launch's items of those variables wait on the
+        device until the int32 counter ``done`` exceeds ``seen`` (ops.epoch_signal after their
+        gradient's producer on another stream); the launch then advances ``seen``."""
         if grad is None and grad16 is None:
             grad = self.P.grad
+        wait = (None, None, 0) if wait is None else (wait[0], wait[1], self._wait_mask(wait[2]))
         if self.device.type == "cuda":
-            ops.apply_gradients(self.kind, self.P.master, grad, grad16, gscale, self.s1, self.s2, c.lr, c.beta1,
-                                c.beta2, c.resolved_eps(), c.momentum, c.rho, self.beta_pow, self.global_step, gs_inc,
-                                self.done, self._blob, self.nseg, self.nwork, group)
+            ops.apply_gradients(self.kind, self.P.master, grad, grad16, gscale, self.s1, self.s2, *self._hyper(),
+                                self.beta_pow, self.global_step, gs_inc, self.done, self._blob, self.nseg,
+                                self.nwork, *wait)
             return
         self._step_cpu(grad if grad is not None else grad16.float(), gscale, gs_inc)
 
@@ -255,8 +267,13 @@ class Optimizer:
         calling ``step`` on each in order."""
         kinds = {o.kind for o in opts}
         if len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and all(o.device.type == "cuda" for o in opts):
-            for i, (o, inc) in enumerate(zip(opts, gs_incs)):
-                o.step(grad=grad, grad16=grad16, gscale=gscale, gs_inc=inc, group=2 if i == len(opts) - 1 else 1)
+            P = opts[0].P
+            assert all(o.P is P for o in opts)
+            ops.require().apply_gradients_group(
+                kinds.pop(), P.master, P.grad if grad is None and grad16 is None else grad, grad16, gscale,
+                [o.s1 for o in opts], [o.s2 for o in opts], [h for o in opts for h in o._hyper()],
+                [o.beta_pow for o in opts], [o.global_step for o in opts], list(gs_incs), [o.done for o in opts],
+                [o._blob for o in opts], [o.nseg for o in opts], [o.nwork for o in opts])
             return
         for o, inc in zip(opts, gs_incs):
             o.step(grad=grad, grad16=grad16, gscale=gscale, gs_inc=inc)

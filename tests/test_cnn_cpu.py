@@ -36,6 +36,25 @@ def autograd_f32(core):
                          "bc2": bc2.grad, "bd1": bd1.grad, "bout": bo.grad}, logits.detach()
 
 
+def test_optimizer_wait_names_become_a_var_list_mask():
+    """Optimizer.step(wait=(done, seen, names)): the names are checked against the optimizer's own
+    var_list (no native library needed); on the CPU a valid wait is ignored."""
+    from dtfe.models.mnist_cnn import var_specs
+    from dtfe.optim import FlatParams, Optimizer, OptimizerConfig
+    specs, n = var_specs()
+    P = FlatParams(specs, "cpu", seed=0)
+    opt = Optimizer(OptimizerConfig(kind="sgd", lr=0.5), P, var_list=[n["wc2"], n["bc2"]])
+    assert opt._wait_mask([n["bc2"]]) == 0b10 and opt._wait_mask([n["wc2"], n["bc2"]]) == 0b11
+    P.grad.fill_(1.0)
+    before = P.master.clone()
+    with pytest.raises(ValueError, match="var_list"):
+        opt.step(wait=(None, None, [n["wc2"], n["wc1"]]))
+    assert torch.equal(P.master, before)
+    wc2 = P.view(n["wc2"]).clone()
+    opt.step(wait=(None, None, [n["wc2"]]))
+    assert torch.equal(P.view(n["wc2"]), wc2 - 0.5)
+
+
 def test_fp32_cnn_step_matches_autograd():
     m = MnistCnnModel()
     m.set_dtype("fp32")

@@ -28,6 +28,19 @@ def test_flip_formulation_is_the_data_gradient_cpu():
     assert torch.allclose(out, x.grad.permute(0, 2, 3, 1), atol=1e-4)
 
 
+def test_no_op_carries_state_to_a_later_call_cpu():
+    """The ops that armed or queued work for a later, unrelated call are gone from the built library:
+    a launch's dependencies are its own arguments (apply_gradients' wait_*, wgrad_reduce_group's lists)."""
+    if not ops.available():
+        pytest.skip("native library not built")
+    lib = ops.require()
+    for name in ("apply_wait_next", "wgrad_flush", "wgrad_pending", "wgrad_discard"):
+        assert not hasattr(lib, name), name
+        assert not hasattr(ops, name), name
+    assert "group" not in str(lib.apply_gradients.default._schema)
+    assert ops.WgradReduces().flush() == 0  # nothing collected: no call into the library
+
+
 CASES = [  # (B, SH, CS, N, K, stride, pad, pool)
     (3, 14, 32, 64, 5, 1, 2, True),     # MNIST conv2 fwd
     (2, 32, 16, 16, 3, 1, 1, False),    # ResNet-20 stage 1
@@ -340,12 +353,12 @@ def test_imgconv_bn_src_cpu_oracle():
 
 @pytest.mark.gpu
 def test_imgwgrad_deferred_reduces_grouped_flush():
-    """Weight gradients whose partial-slab reduces are queued (defer=True, own workspaces) and summed
-    by ONE grouped launch (ops.wgrad_flush) == the per-call reduce, bit for bit."""
+    """Weight gradients whose partial-slab reduces are left to a collector (defer=ops.WgradReduces(),
+    own workspaces) and summed by ONE grouped launch (its flush) == the per-call reduce, bit for bit."""
     torch.manual_seed(16)
     shapes = [(256, 32, 16, 16, 1), (256, 16, 32, 32, 1), (256, 8, 64, 64, 1), (256, 32, 16, 32, 2)]
-    ref, got, ws = [], [], []
-    args = []
+    ref, got = [], []
+    args, reduces = [], ops.WgradReduces()
     for B, SH, CS, N, s in shapes:
         OH = (SH + 2 - 3) // s + 1
         x = torch.randn(B, SH, SH, CS).to(DEV, torch.bfloat16)
@@ -358,11 +371,10 @@ def test_imgwgrad_deferred_reduces_grouped_flush():
     for x, dy, kw in args:
         g = torch.zeros(kw["N"], 3, 3, kw["CS"], device=DEV)
         w = torch.empty(ops.wgrad_ws_floats(kw["N"], 9 * kw["CS"]), device=DEV)
-        ops.imgwgrad(x, g, None, dy=dy, workspace=w, defer=True, **kw)
+        ops.imgwgrad(x, g, None, dy=dy, workspace=w, defer=reduces, **kw)
         got.append(g)
-        ws.append(w)
-    assert ops.wgrad_flush() == len(shapes)
+    assert len(reduces) == len(shapes) and reduces.flush() == len(shapes)
     torch.cuda.synchronize()
     for a, b in zip(got, ref):
         assert torch.equal(a, b)
-    assert ops.wgrad_flush() == 0
+    assert reduces.flush() == 0

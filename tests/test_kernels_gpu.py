@@ -427,6 +427,33 @@ def test_grouped_apply_equals_separate_launches():
     assert res[1][5] == 6
 
 
+def test_apply_wait_arguments_do_not_outlive_their_call():
+    """apply_gradients(wait_done=, wait_seen=, wait_segs=): the wait belongs to that one launch (it
+    advances ``seen`` once; the producer signalled earlier on the same stream, so nothing spins) and
+    a later plain launch neither waits nor touches the counters; parameters equal, bitwise, the same
+    two applies without wait arguments."""
+    torch.manual_seed(11)
+    n0, n1 = 3000, 2000
+    segs = torch.tensor([[0, n0, 1, 1, 0, 0], [n0, n1, 1, 1, 0, 0]], dtype=torch.int64)
+    work = torch.tensor([[0, 0, 0, 0, 0, 0, n0], [0, 1, 0, 0, 0, 0, n1]], dtype=torch.int64)
+    p0 = torch.randn(n0 + n1, device=DEV)
+    g = torch.randn(n0 + n1, device=DEV)
+    blob = ops.opt_pack(segs, work, p0)
+    opt_done, done, seen = (torch.zeros(1, dtype=torch.int32, device=DEV) for _ in range(3))
+    res = []
+    for wait in ({}, dict(wait_done=done, wait_seen=seen, wait_segs=0b10)):
+        p = p0.clone()
+        if wait:
+            ops.epoch_signal(done)
+        for w in (wait, {}):
+            ops.apply_gradients(ops.OPT_SGD, p, g, None, 1.0, None, None, 0.1, 0, 0, 0, 0, 0, None, None, 0, opt_done,
+                                blob, 2, 2, **w)
+        torch.cuda.synchronize()
+        res.append(p)
+    assert torch.equal(res[0], res[1]) and not torch.equal(res[0], p0)
+    assert int(done.item()) == 1 and int(seen.item()) == 1
+
+
 def test_uniform_fill_fused_copy():
     x = torch.randn(128, 784, device=DEV)
     dst = torch.zeros(256, 784, device=DEV)

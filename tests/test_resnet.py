@@ -453,7 +453,7 @@ def test_resnet20_bn_src_fold_matches_materialised_gpu(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------
-# Round 6: evaluation at the fold / fused-head batch sizes, the deferred weight-gradient queue,
+# Round 6: evaluation at the fold / fused-head batch sizes, the deferred weight-gradient reduces,
 # the per-bucket grouped flush of the multi-rank schedules, and the bench-shaped step vs fp32.
 
 class _Hook:
@@ -523,26 +523,31 @@ def test_resnet20_evaluate_at_fold_batch_gpu():
 
 
 @pytest.mark.gpu
-def test_resnet20_deferred_queue_guard_gpu(monkeypatch):
-    """A deferred weight-gradient reduce left in the queue (a stray imgwgrad(defer=True), or a
-    backward interrupted between its deferred launches and the flush) makes the next backward fail
-    loudly and is discarded; an exception inside backward leaves the queue empty."""
+def test_resnet20_deferred_reduces_owned_by_program_gpu(monkeypatch):
+    """Deferred weight-gradient reduces live in the collector of whoever deferred them: a stray
+    imgwgrad(defer=<throw-away collector>) that is never flushed, and a backward interrupted between
+    its deferred launches and the flush, change nothing in the program's later backwards (equal to
+    a clean run within the run-to-run noise of the BN statistics' atomics), and the program's
+    collector is empty after the failed and after the good backward."""
     from dtfe import ops
     B = 128
     prog = ResNetModel(arch="resnet20").program("cuda", B, seed=1)
     x = torch.rand(B, 32, 32, 3, device="cuda")
     y = F.one_hot(torch.randint(0, 10, (B,), device="cuda"), 10).float()
     prog.load_batch((x, y))
-    prog.compute_grads()
-    assert prog.defer_wgrad and ops.wgrad_pending() == 0
+    runs = []
+    for _ in range(2):  # the baseline and a second clean run (the noise floor)
+        m = prog.compute_grads()
+        torch.cuda.synchronize()
+        runs.append((float(m["loss"]), prog.P.grad.clone()))
+    assert prog.defer_wgrad and len(prog._reduces) == 0
     c = prog._defer_convs[0]
     dy = torch.randn(B, c.OH, c.OW, c.cout, device="cuda").to(torch.bfloat16)
     src = torch.randn(B, c.H, c.W, c.cin, device="cuda").to(torch.bfloat16)
-    ops.imgwgrad(src, torch.zeros_like(c.gw), None, dy=dy, workspace=prog._defer_ws[c], defer=True, **c.ic)
-    assert ops.wgrad_pending() == 1
-    with pytest.raises(RuntimeError, match="deferred weight-gradient"):
-        prog.compute_grads()
-    assert ops.wgrad_pending() == 0
+    stray = ops.WgradReduces()
+    ops.imgwgrad(src, torch.zeros_like(c.gw), None, dy=dy, defer=stray, **c.ic,
+                 workspace=torch.empty(ops.wgrad_ws_floats(c.cout, c.k * c.k * c.cin), device="cuda"))
+    assert len(stray) == 1 and len(prog._reduces) == 0
     # an exception after some deferred launches: nothing survives into the next backward
     blk = prog.L["blocks"][0]
     real = blk.bwd
@@ -550,13 +555,16 @@ def test_resnet20_deferred_queue_guard_gpu(monkeypatch):
     def boom(*a, **k):
         raise ValueError("injected")
     monkeypatch.setattr(blk, "bwd", boom)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="injected"):
         prog.compute_grads()
-    assert ops.wgrad_pending() == 0
+    assert len(prog._reduces) == 0
     monkeypatch.setattr(blk, "bwd", real)
-    prog.compute_grads()
+    m = prog.compute_grads()
     torch.cuda.synchronize()
-    assert ops.wgrad_pending() == 0 and torch.isfinite(prog.P.grad).all()
+    assert len(prog._reduces) == 0 and len(stray) == 1 and torch.isfinite(prog.P.grad).all()
+    (l0, g0), (l1, g1), (l2, g2) = runs + [(float(m["loss"]), prog.P.grad)]
+    assert abs(l2 - l0) <= 4 * abs(l1 - l0) + 1e-3 * abs(l0)
+    assert _rel(g2, g0) <= 4 * _rel(g1, g0) + 1e-3, (_rel(g2, g0), _rel(g1, g0))
 
 
 @pytest.mark.gpu
@@ -571,12 +579,12 @@ def test_wgrad_grouped_flush_bitwise_gpu():
     ins = [(torch.randn(B, c.H, c.W, c.cin, device="cuda").to(torch.bfloat16),
             torch.randn(B, c.OH, c.OW, c.cout, device="cuda").to(torch.bfloat16)) for c in convs]
     outs = []
-    for defer in (False, True):
+    for defer in (None, ops.WgradReduces()):
         dws = [torch.full_like(c.gw, 0.5) for c in convs]
         for c, (src, dy), dw in zip(convs, ins, dws):
             ops.imgwgrad(src, dw, None, dy=dy, workspace=prog._defer_ws[c], defer=defer, **c.ic)
-        if defer:
-            assert ops.wgrad_flush() == len(convs)
+        if defer is not None:
+            assert defer.flush() == len(convs)
         torch.cuda.synchronize()
         outs.append(dws)
     for a, b in zip(*outs):
@@ -590,26 +598,28 @@ def test_resnet20_bucket_flush_matches_per_call_reduce_gpu(monkeypatch, nb):
     (nb + at most 1 grouped launches instead of one reduce per conv) give the per-call reduce's
     gradients, within the run-to-run noise of the BN statistics' atomics."""
     import dtfe.models.resnet as R
-    from dtfe import ops
     B = 256
     torch.manual_seed(0)
     x = torch.rand(B, 32, 32, 3).cuda()
     y = F.one_hot(torch.randint(0, 10, (B,)), 10).float().cuda()
     flushes = []
-    real_flush = ops.wgrad_flush
 
-    def counting_flush():
-        n = real_flush()
-        if n:
-            flushes.append(n)
-        return n
-    monkeypatch.setattr(ops, "wgrad_flush", counting_flush)
+    def count_flushes(reduces):
+        real_flush = reduces.flush
+
+        def counting_flush():
+            n = real_flush()
+            if n:
+                flushes.append(n)
+            return n
+        monkeypatch.setattr(reduces, "flush", counting_flush)
     runs = []
     for defer in (False, False, True):
         monkeypatch.setattr(R, "_WGRAD_DEFER", defer)
         prog = ResNetModel(arch="resnet20").program("cuda", B, seed=3)
         hook = _Hook(_r20_buckets(prog, nb))
         prog.grad_ready = hook.ready
+        count_flushes(prog._reduces)
         prog.load_batch((x, y))
         m = prog.compute_grads()
         torch.cuda.synchronize()
