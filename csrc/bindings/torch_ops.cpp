@@ -5,6 +5,7 @@
 // captured into a hipGraph (torch.cuda.CUDAGraph) with zero allocations.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
+#include <torch/custom_class.h>
 #include <torch/library.h>
 #include <vector>
 
@@ -41,6 +42,34 @@ int dtype_code(const Tensor& t) {
 }
 
 // ------------------------------------------------------------------- gemm
+// torch.classes.dtfe.GemmGroup: the pieces of one grouped launch (gemm_dense.h), added by gemm /
+// head_wgrad calls that name the group, plus references to the tensors whose pointers the pieces
+// hold - kept until launch() or clear().  Destroying a non-empty group launches nothing.
+struct GemmGroupObj : torch::CustomClassHolder {
+  dtfe::GemmGroup g;
+  std::vector<Tensor> held;
+  int dev = -1;  // device index of the pieces
+  void hold(const Tensor& t) { held.push_back(t); }
+  void hold(const optional<Tensor>& t) { if (t.has_value() && t->defined()) held.push_back(*t); }
+  // a piece on the device of tensor `on`: add(g) records it (false: it does not fit, the caller launches it now)
+  template <typename F, typename... T>
+  bool join(F&& add, const Tensor& on, const T&... rest) {
+    TORCH_CHECK(dev < 0 || dev == on.get_device(), "gemm group: a piece on device ", on.get_device(),
+                " cannot join a group on device ", dev);
+    if (!add(g)) return false;
+    dev = on.get_device();
+    (hold(on), ..., hold(rest));
+    return true;
+  }
+  void clear() { g = dtfe::GemmGroup(); held.clear(); dev = -1; }
+  void launch() {  // on the current stream of the pieces' device; an empty group does nothing
+    if (g.pieces()) dtfe::launch_gemm_group(g, at::hip::getCurrentHIPStream(dev).stream());
+    clear();
+  }
+  int64_t pieces() const { return g.pieces(); }
+};
+using GroupArg = optional<c10::intrusive_ptr<GemmGroupObj>>;
+
 void gemm(const Tensor& A, int64_t amode, int64_t lda, const Tensor& B, int64_t bmode, int64_t ldb, int64_t M,
           int64_t N, int64_t K, const Tensor& out, int64_t ldc, const optional<Tensor>& bias, int64_t bias_axis,
           int64_t act, double alpha, double beta, bool atomic, int64_t splits, int64_t tile,
@@ -48,7 +77,7 @@ void gemm(const Tensor& A, int64_t amode, int64_t lda, const Tensor& B, int64_t 
           const optional<Tensor>& counter, const optional<Tensor>& pooled, const optional<Tensor>& argmax,
           int64_t PH, int64_t PW, int64_t PC, const optional<Tensor>& out2, int64_t ldc2, bool out2_trans,
           const optional<Tensor>& bias_out, const optional<Tensor>& ws, const optional<Tensor>& tile_ctr,
-          int64_t a_ones_row, const optional<Tensor>& ones) {
+          int64_t a_ones_row, const optional<Tensor>& ones, const GroupArg& group) {
   check_cuda(A, "A");
   check_cuda(B, "B");
   check_cuda(out, "out");
@@ -114,15 +143,12 @@ void gemm(const Tensor& A, int64_t amode, int64_t lda, const Tensor& B, int64_t 
     const int64_t b_need = bmode == 0 ? (b_rows - 1) * ldb + K : (K - 1) * ldb + b_rows;
     TORCH_CHECK(A.numel() >= a_need && B.numel() >= b_need, "gemm: operands smaller than M/N/K/ld imply");
   }
+  auto add = [&](dtfe::GemmGroup& g) {
+    return dtfe::gemm_group_add(g, dt == 0 ? 0 : 1, (int)amode, (int)bmode, (int)tile, real_splits, a);
+  };  // (a piece has one split: no ws / tile_ctr to hold)
+  if (group.has_value() && (*group)->join(add, out, A, B, bias, aux, counter, pooled, argmax, out2, bias_out, ones))
+    return;
   dtfe::launch_gemm_dense(dt == 0 ? 0 : 1, (int)amode, (int)bmode, (int)tile, real_splits, a, cur_stream());
-}
-
-// gemm_group(anchor, begin): begin / end a grouped launch on the current stream (gemm_dense.h);
-// `anchor` is any tensor on the launch device (dispatch only)
-void gemm_group(const Tensor& anchor, bool begin) {
-  check_cuda(anchor, "anchor");
-  if (begin) dtfe::glds_group_begin();
-  else dtfe::glds_group_end(cur_stream());
 }
 
 // ------------------------------------------------------------------- conv
@@ -517,7 +543,7 @@ void head_xent(const Tensor& h, const Tensor& w, const optional<Tensor>& b, cons
 
 void head_wgrad(const Tensor& dl, const Tensor& h, const Tensor& dw, const optional<Tensor>& db, int64_t nc,
                 double scale, const optional<Tensor>& parts, const optional<Tensor>& loss_sum,
-                const optional<Tensor>& correct) {
+                const optional<Tensor>& correct, const GroupArg& group) {
   check_cuda(h, "h");
   TORCH_CHECK(dl.scalar_type() == at::kBFloat16 && h.scalar_type() == at::kBFloat16 && dl.dim() == 2 && h.dim() == 2,
               "head_wgrad: bf16 dl [B][ld] and h [B][K]");
@@ -544,6 +570,8 @@ void head_wgrad(const Tensor& dl, const Tensor& h, const Tensor& dw, const optio
     a.parts = parts->data_ptr<float>(); a.nparts = (a.B + 3) / 4;
     a.loss_sum = loss_sum->data_ptr<float>(); a.correct = correct->data_ptr<int32_t>();
   }
+  auto add = [&](dtfe::GemmGroup& g) { return dtfe::gemm_group_add_head(g, a); };
+  if (group.has_value() && (*group)->join(add, h, dl, dw, db, parts, loss_sum, correct)) return;
   dtfe::launch_head_wgrad(a, cur_stream());
 }
 
@@ -1239,12 +1267,19 @@ TORCH_LIBRARY(dtfe, m) {
         " float forget_bias) -> ()");
   m.def("lstm_cell_bwd(Tensor act, Tensor? c_prev, Tensor c, Tensor? dh, Tensor? dh2, Tensor? dc_next,"
         " Tensor(a!) dgates, Tensor(b!) dc_prev) -> ()");
+  // (registered before the schemas that name it)
+  m.class_<GemmGroupObj>("GemmGroup")
+      .def(torch::init<>())
+      .def("launch", &GemmGroupObj::launch)
+      .def("clear", &GemmGroupObj::clear)
+      .def("pieces", &GemmGroupObj::pieces);
   m.def(
       "gemm(Tensor A, int amode, int lda, Tensor B, int bmode, int ldb, int M, int N, int K, Tensor(a!) out, int ldc,"
       " Tensor? bias, int bias_axis, int act, float alpha, float beta, bool atomic, int splits, int tile,"
       " Tensor? aux, int ld_aux, int aux_act, int b_ones_row, float keep, int seed, Tensor? counter,"
       " Tensor? pooled, Tensor? argmax, int PH, int PW, int PC, Tensor(b!)? out2, int ldc2, bool out2_trans,"
-      " Tensor(c!)? bias_out, Tensor(d!)? ws, Tensor(e!)? tile_ctr, int a_ones_row=-1, Tensor? ones=None) -> ()");
+      " Tensor(c!)? bias_out, Tensor(d!)? ws, Tensor(e!)? tile_ctr, int a_ones_row=-1, Tensor? ones=None,"
+      " __torch__.torch.classes.dtfe.GemmGroup? group=None) -> ()");
   m.def(
       "conv_fwd(Tensor x, Tensor w, Tensor? bias, Tensor(a!) y, Tensor(b!)? argmax, int B, int H, int W, int C,"
       " int Cout, int OH, int OW, int KH, int KW, int stride, int pad, bool pool, int act, Tensor(c!)? bn_stats=None)"
@@ -1278,8 +1313,8 @@ TORCH_LIBRARY(dtfe, m) {
       " Tensor(c!)? loss_sum, Tensor(d!)? correct, Tensor(e!)? logits, float scale, float inv_keep,"
       " Tensor(f!)? step_counter=None, Tensor(g!)? parts=None) -> ()");
   m.def("head_wgrad(Tensor dl, Tensor h, Tensor(a!) dw, Tensor(b!)? db, int nc, float scale, Tensor? parts=None,"
-        " Tensor(c!)? loss_sum=None, Tensor(d!)? correct=None) -> ()");
-  m.def("gemm_group(Tensor anchor, bool begin) -> ()");
+        " Tensor(c!)? loss_sum=None, Tensor(d!)? correct=None,"
+        " __torch__.torch.classes.dtfe.GemmGroup? group=None) -> ()");
   m.def("opt_pack(Tensor segs, Tensor work, Tensor device_like) -> Tensor");
   m.def(
       "apply_gradients(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor(b!)? s1, Tensor(c!)? s2,"
@@ -1344,7 +1379,6 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("conv_wgrad", &conv_wgrad);
   m.impl("head_xent", &head_xent);
   m.impl("head_wgrad", &head_wgrad);
-  m.impl("gemm_group", &gemm_group);
   m.impl("apply_gradients", &apply_gradients);
   m.impl("apply_gradients_group", &apply_gradients_group);
   m.impl("gather_rows", &gather_rows);

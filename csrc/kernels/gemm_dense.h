@@ -3,6 +3,7 @@
 #pragma once
 #include "gemm_core.h"
 #include "conv.h"
+#include "head.h"
 
 namespace dtfe {
 
@@ -267,18 +268,30 @@ void launch_gemm_dense(int dtype, int amode, int bmode, int tile, int splits, co
 constexpr int GEMM_TILE_SMALL = 13;
 bool gemm_small_eligible(int dtype, const DenseGemmArgs& a);
 void launch_gemm_small(int amode, int bmode, const DenseGemmArgs& a, hipStream_t s);
-// n (<= 2) small GEMMs recorded inside a gemm group: a (RMAJ, RMAJ) + (KMAJ, KMAJ) pair leaves as one
-// launch, anything else launches one by one in recording order
+// the n (<= 2) small GEMMs of a GemmGroup: a (RMAJ, RMAJ) + (KMAJ, KMAJ) pair leaves as one
+// launch, anything else launches one by one in the order added
 void launch_gemm_small_group(int n, const int* am, const int* bm, const DenseGemmArgs* g, hipStream_t s);
-// Grouped launch (gemm_dense.hip): between begin and end, launch_gemm_dense calls with glds tile 12
-// or 22 (both pieces the same tile) and one split, and launch_head_wgrad calls, are recorded instead of launched (record functions
-// return false when a call does not fit the group); end launches the recorded pieces as one grid
-// (head weight gradient, then a (KMAJ, RMAJ) and a (RMAJ, RMAJ) GEMM), or one by one otherwise.
-struct HeadWgradArgs;
-void glds_group_begin();
-bool glds_group_record(int amode, int bmode, int tile, const DenseGemmArgs& a);
-bool glds_group_record_head(const HeadWgradArgs& a);
-void glds_group_end(hipStream_t s);
+// Grouped launch (gemm_dense.hip): the caller owns a GemmGroup and adds the pieces meant to leave
+// together; an add that returns false does not fit (the caller launches that piece itself).  Held:
+// up to two bf16 one-split glds GEMMs of tile 12 or 22 (both the same tile), up to two fp32
+// small-tile GEMMs (tile 13), one head weight gradient (B <= 1024).  launch_gemm_group launches and
+// empties the group: the small pieces through launch_gemm_small_group; the head weight gradient
+// with a (KMAJ, RMAJ) and a (RMAJ, RMAJ) glds GEMM as one grid, any other mix one by one (head
+// first, then the GEMMs in the order added).  The arguments hold raw device pointers: the owner
+// keeps the tensors alive until the launch.
+struct GemmGroup {
+  int tile = 12;  // the glds pieces' tile: 12 (64x64) or 22 (the 8-wave fc tile, gemm_fc.hip)
+  int ng = 0, am[2] = {0, 0}, bm[2] = {0, 0};
+  DenseGemmArgs g[2];
+  int ns = 0, sam[2] = {0, 0}, sbm[2] = {0, 0};  // the small-tile pieces (gemm_small.hip)
+  DenseGemmArgs s[2];
+  bool has_h = false;
+  HeadWgradArgs h;
+  int pieces() const { return ng + ns + (has_h ? 1 : 0); }
+};
+bool gemm_group_add(GemmGroup& grp, int dtype, int amode, int bmode, int tile, int splits, const DenseGemmArgs& a);
+bool gemm_group_add_head(GemmGroup& grp, const HeadWgradArgs& a);
+void launch_gemm_group(GemmGroup& grp, hipStream_t s);
 // block tile of a tile id; returns the k-tile depth (split-K chunks are multiples of it)
 int gemm_dense_tile_dims(int tile, int& bm, int& bn);
 // whether the global_load_lds kernel family can run this GEMM with tile `tile` (5..8)

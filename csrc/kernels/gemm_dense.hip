@@ -105,20 +105,15 @@ static void by_mode(int am, int bm, int tile, int splits, const DenseGemmArgs& a
   else by_tile<T, RMAJ, RMAJ>(tile, splits, a, s);
 }
 
-static bool small_group_record(int amode, int bmode, const DenseGemmArgs& a);
-
 void launch_gemm_dense(int dtype, int amode, int bmode, int tile, int splits, const DenseGemmArgs& args,
                        hipStream_t stream) {
   if (splits < 1) splits = 1;
   if (tile == GEMM_TILE_SMALL) {
     if (!gemm_small_eligible(dtype, args) || splits != 1)
       throw std::runtime_error("gemm_dense: the small-tile kernel takes fp32, one split, no un-pool epilogue");
-    if (small_group_record(amode, bmode, args)) return;  // inside a group
     launch_gemm_small(amode, bmode, args, stream);
     return;
   }
-  if ((tile == 12 || tile == FC_TILE) && splits == 1 && dtype == 0 && glds_group_record(amode, bmode, tile, args))
-    return;  // inside a group
   if (tile == FC_TILE) {
     if (!gemm_fc_eligible(dtype, amode, bmode, args))
       throw std::runtime_error("gemm_dense: this GEMM is not eligible for tile 22 (gemm_fc_eligible)");
@@ -178,67 +173,42 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_glds_group_kernel(GlGrou
   if (bid < ga.t1) gemm_glds_body<64, 64, AM1, BM1, 2>(ga.g1, bid, smem_raw);
 }
 
-namespace {
-struct GlGroupRec {
-  bool active = false;
-  int tile = 12;  // the pieces' tile: 12 (64x64 glds) or 22 (the 8-wave fc tile, gemm_fc.hip)
-  int ng = 0, am[2] = {0, 0}, bm[2] = {0, 0};
-  DenseGemmArgs g[2];
-  bool has_h = false;
-  HeadWgradArgs h;
-};
-thread_local GlGroupRec g_group;
-int pad8(int n) { return (n + 7) / 8 * 8; }
-struct SmallGroupRec {  // the fp32 small-tile pieces of the same group (gemm_small.hip)
-  int n = 0, am[2] = {0, 0}, bm[2] = {0, 0};
-  DenseGemmArgs g[2];
-};
-thread_local SmallGroupRec g_small;
-}  // namespace
+static int pad8(int n) { return (n + 7) / 8 * 8; }
 
-static bool small_group_record(int amode, int bmode, const DenseGemmArgs& a) {
-  if (!g_group.active || g_small.n == 2) return false;
-  g_small.am[g_small.n] = amode;
-  g_small.bm[g_small.n] = bmode;
-  g_small.g[g_small.n++] = a;
-  return true;
-}
-
-void glds_group_begin() {
-  if (g_group.active) throw std::runtime_error("gemm group: already recording");
-  g_group = GlGroupRec();
-  g_small = SmallGroupRec();
-  g_group.active = true;
-}
-
-bool glds_group_record(int amode, int bmode, int tile, const DenseGemmArgs& a) {
-  if (!g_group.active || g_group.ng == 2) return false;
-  if (g_group.ng == 1 && g_group.tile != tile) return false;
+bool gemm_group_add(GemmGroup& grp, int dtype, int amode, int bmode, int tile, int splits, const DenseGemmArgs& a) {
+  if (splits > 1) return false;
+  if (tile == GEMM_TILE_SMALL) {
+    if (grp.ns == 2 || !gemm_small_eligible(dtype, a)) return false;
+    grp.sam[grp.ns] = amode;
+    grp.sbm[grp.ns] = bmode;
+    grp.s[grp.ns++] = a;
+    return true;
+  }
+  if ((tile != 12 && tile != FC_TILE) || dtype != 0 || grp.ng == 2) return false;
+  if (grp.ng == 1 && grp.tile != tile) return false;
   if (!gemm_glds_eligible(0, amode, bmode, tile, a)) return false;
-  g_group.tile = tile;
-  g_group.am[g_group.ng] = amode;
-  g_group.bm[g_group.ng] = bmode;
-  g_group.g[g_group.ng++] = a;
+  grp.tile = tile;
+  grp.am[grp.ng] = amode;
+  grp.bm[grp.ng] = bmode;
+  grp.g[grp.ng++] = a;
   return true;
 }
 
-bool glds_group_record_head(const HeadWgradArgs& a) {
-  if (!g_group.active || g_group.has_h || a.B > 1024) return false;
-  g_group.has_h = true;
-  g_group.h = a;
+bool gemm_group_add_head(GemmGroup& grp, const HeadWgradArgs& a) {
+  check_head_wgrad(a);  // (B <= 1024 among the rest: the grouped head bodies stream any such batch)
+  if (grp.has_h) return false;
+  grp.has_h = true;
+  grp.h = a;
   return true;
 }
 
-void glds_group_end(hipStream_t s) {
-  if (!g_group.active) throw std::runtime_error("gemm group: not recording");
-  GlGroupRec r = g_group;
-  g_group = GlGroupRec();
-  const SmallGroupRec sr = g_small;
-  g_small = SmallGroupRec();
-  if (sr.n) launch_gemm_small_group(sr.n, sr.am, sr.bm, sr.g, s);
+void launch_gemm_group(GemmGroup& grp, hipStream_t s) {
+  const GemmGroup r = grp;
+  grp = GemmGroup();
+  if (r.ns) launch_gemm_small_group(r.ns, r.sam, r.sbm, r.s, s);
   if (r.ng == 0 && !r.has_h) return;
   const bool fused = r.ng == 2 && r.am[0] == KMAJ && r.bm[0] == RMAJ && r.am[1] == RMAJ && r.bm[1] == RMAJ;
-  if (!fused) {  // any other combination: the pieces as separate launches, in recording order
+  if (!fused) {  // any other combination: the pieces as separate launches, in the order added
     if (r.has_h) launch_head_wgrad(r.h, s);
     for (int i = 0; i < r.ng; ++i) launch_gemm_dense(0, r.am[i], r.bm[i], r.tile, 1, r.g[i], s);
     return;

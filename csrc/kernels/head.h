@@ -56,6 +56,8 @@ struct HeadWgradArgs {
   const float* parts; int nparts; float* loss_sum; int32_t* correct;
 };
 void launch_head_wgrad(const HeadWgradArgs& a, hipStream_t s);
+// throws unless launch_head_wgrad (or a grouped launch's head piece, gemm_dense.h) can run `a`
+void check_head_wgrad(const HeadWgradArgs& a);
 
 // Bias workgroup: loss_sum += sum(parts[0:n]), correct += sum(parts[n:2n]) (wave 0, lane-strided
 // partial sums, then a butterfly: lane 0's total has a fixed summation order)

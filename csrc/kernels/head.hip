@@ -236,12 +236,15 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(HeadWgradArgs a) {
   head_wgrad_body<NC, ROWS>(a, blockIdx.x, red);
 }
 
-void launch_head_wgrad(const HeadWgradArgs& a, hipStream_t s) {
+void check_head_wgrad(const HeadWgradArgs& a) {
   if (a.NC != 10 || a.K % 8 || a.ld_dl < 16 || a.ld_dl % 8 || a.ldh % 8 || a.B > 1024)
     throw std::runtime_error("head_wgrad: needs NC=10, K % 8 == 0, 16-B aligned dl rows of >= 16 and h rows, B <= 1024");
   if (a.parts && (!a.db || !a.loss_sum || !a.correct))
     throw std::runtime_error("head_wgrad: folding the loss partials needs db (the bias workgroup), loss_sum and correct");
-  if (glds_group_record_head(a)) return;  // recorded into a grouped launch (gemm_dense.hip)
+}
+
+void launch_head_wgrad(const HeadWgradArgs& a, hipStream_t s) {
+  check_head_wgrad(a);
   const int blocks = a.K / 8 + (a.db ? 1 : 0);
   if (a.B <= 256) hipLaunchKernelGGL((head_wgrad_kernel<10, 1>), dim3(blocks), dim3(256), 0, s, a);
   else if (a.B <= 512) hipLaunchKernelGGL((head_wgrad_kernel<10, 2>), dim3(blocks), dim3(256), 0, s, a);

@@ -96,12 +96,14 @@ class AutoencoderProgram(StepProgram):
         for i in range(3, -1, -1):
             inp = self.xin if i == 0 else self.a[i - 1]
             # a layer's weight and data gradients are independent: one paired launch (ops.gemm_group)
-            with ops.gemm_group(self.loss):
+            with ops.gemm_group(self.loss) as grp:
                 # dW_i[K][N] = inp^T . dz_i ; db_i = sum_b dz_i through the GEMM's ones row (no colsum launch)
                 ops.gemm(inp, self.dz[i], self.gW[i], M=DIMS[i] + 1, N=DIMS[i + 1], K=B, amode=ops.RMAJ,
-                         lda=DIMS[i], bmode=ops.RMAJ, ldb=DIMS[i + 1], a_ones_row=DIMS[i], bias_out=self.gb[i])
+                         lda=DIMS[i], bmode=ops.RMAJ, ldb=DIMS[i + 1], a_ones_row=DIMS[i], bias_out=self.gb[i],
+                         group=grp)
                 if i > 0:
                     # dz_{i-1} = (dz_i . W_i^T) * sigmoid'(a_{i-1})
                     ops.gemm(self.dz[i], self.W[i], self.dz[i - 1], M=B, N=DIMS[i], K=DIMS[i + 1],
-                             bmode=ops.KMAJ, ldb=DIMS[i + 1], aux=self.a[i - 1], aux_act=ops.ACT_SIGMOID)
+                             bmode=ops.KMAJ, ldb=DIMS[i + 1], aux=self.a[i - 1], aux_act=ops.ACT_SIGMOID,
+                             group=grp)
         return {"loss": self.loss}

@@ -140,17 +140,17 @@ class GanProgram(StepProgram):
             ops.gemm(self.dlog_g, W["Wd2"], self.ddf, M=B, N=DH, K=1, amode=K, lda=1, bmode=K, ldb=1,
                      aux=self.d1[B:], aux_act=ops.ACT_RELU)
         # each (weight gradient, data gradient) pair below is independent: one paired launch (ops.gemm_group)
-        with ops.gemm_group(self.d1):
+        with ops.gemm_group(self.d1) as grp:
             ops.gemm(self.xx, self.dd1, G["Wd1"], M=IMG + 1, N=DH, K=2 * B, amode=R, lda=IMG, bmode=R, ldb=DH,
-                     a_ones_row=IMG, bias_out=G["bd1"])
+                     a_ones_row=IMG, bias_out=G["bd1"], group=grp)
             # ---- generator: d gen_loss through D (same parameter snapshot)
             ops.gemm(self.ddf, W["Wd1"], self.dg, M=B, N=IMG, K=DH, amode=K, lda=DH, bmode=K, ldb=DH,
-                     aux=self.xx[B:], aux_act=ops.ACT_SIGMOID)
-        with ops.gemm_group(self.d1):
+                     aux=self.xx[B:], aux_act=ops.ACT_SIGMOID, group=grp)
+        with ops.gemm_group(self.d1) as grp:
             ops.gemm(self.h1, self.dg, G["Wg2"], M=GH + 1, N=IMG, K=B, amode=R, lda=GH, bmode=R, ldb=IMG,
-                     a_ones_row=GH, bias_out=G["bg2"])
+                     a_ones_row=GH, bias_out=G["bg2"], group=grp)
             ops.gemm(self.dg, W["Wg2"], self.dh1, M=B, N=GH, K=IMG, amode=K, lda=IMG, bmode=K, ldb=IMG,
-                     aux=self.h1, aux_act=ops.ACT_RELU)
+                     aux=self.h1, aux_act=ops.ACT_RELU, group=grp)
         ops.gemm(self.z, self.dh1, G["Wg1"], M=NOISE + 1, N=GH, K=B, amode=R, lda=NOISE, bmode=R, ldb=GH,
                  a_ones_row=NOISE, bias_out=G["bg1"])
         return {"gen_loss": self.gen_loss, "disc_loss": self.disc_loss}

@@ -314,10 +314,10 @@ class MnistCnnTrainer:
         # fc backward: head weight gradient, fc1 data gradient, fc1 weight gradient - ONE grouped
         # launch on the GPU (ops.gemm_group; no fork / join of an fc side branch, whose cross-queue
         # edges cost 5-11 us of idle time each in the captured graph)
-        with ops.gemm_group(self.dzf):
-            self._head_wgrad()
-            self._fc1_dgrad(B, K1)
-            self._fc1_wgrad(B, K1)
+        with ops.gemm_group(self.dzf) as grp:
+            self._head_wgrad(grp)
+            self._fc1_dgrad(B, K1, grp)
+            self._fc1_wgrad(B, K1, grp)
         if self.allreduce is not None:
             self.allreduce.launch(0)  # bucket 0 (head + fc1, 98% of the bytes) overlaps the conv backward
             self.schedule.append("allreduce:0")
@@ -353,9 +353,9 @@ class MnistCnnTrainer:
             self.opt_conv.step(grad16=self._late[0], gscale=self._late[1], gs_inc=1)
         return signal
 
-    def _head_wgrad(self):
-        """head wgrad: dW[10][1024] = dlogit^T . H, db = sum dlogit (dedicated whole-batch kernel; the
-        split-K GEMM path takes B > 1024)"""
+    def _head_wgrad(self, grp):
+        """head wgrad: dW[10][1024] = dlogit^T . H, db = sum dlogit (dedicated whole-batch kernel, which
+        joins the fc backward's group; the split-K GEMM path takes B > 1024 and launches at once)"""
         if self.head_gemm:
             ops.gemm(self.dl, self.h, self.gw["out"], M=NCLS, N=FC + 1, K=self.B, amode=ops.RMAJ,
                      lda=self.dl.shape[1], bmode=ops.RMAJ, ldb=FC, ldc=FC, b_ones_row=FC, bias_out=self.gw["bout"],
@@ -364,17 +364,18 @@ class MnistCnnTrainer:
             # B <= 1024; its bias workgroup also folds head_xent's loss / hit partials into
             # loss_sum / correct (256 same-address atomics cost ~2.5 us of head_xent's 7.8)
             ops.head_wgrad(self.dl, self.h, self.gw["out"], self.gw["bout"], NCLS, parts=self.head_parts,
-                           loss_sum=self.loss_sum, correct=self.correct)
+                           loss_sum=self.loss_sum, correct=self.correct, group=grp)
 
-    def _fc1_wgrad(self, B, K1):
+    def _fc1_wgrad(self, B, K1, grp):
         """fc1 wgrad: dW[1024][3136] = dZf^T . P2 ; bias grad = sum dZf via the ones column."""
         ops.gemm(self.dzf, self.p2, self.gw["wd1"], M=FC, N=K1 + 1, K=B, amode=ops.RMAJ, lda=FC,
-                 bmode=ops.RMAJ, ldb=K1, ldc=K1, b_ones_row=K1, bias_out=self.gw["bd1"], tile=self.t_wgrad)
+                 bmode=ops.RMAJ, ldb=K1, ldc=K1, b_ones_row=K1, bias_out=self.gw["bd1"], tile=self.t_wgrad,
+                 group=grp)
 
-    def _fc1_dgrad(self, B, K1):
+    def _fc1_dgrad(self, B, K1, grp):
         """fc1 dgrad -> dP2 at pooled resolution, ReLU'(P2)-masked (consumers un-pool on load)."""
         ops.gemm(self.dzf, self.w["wd1"], self.dp2, M=B, N=K1, K=FC, bmode=ops.RMAJ, ldb=K1, aux=self.p2,
-                 aux_act=ops.ACT_RELU, tile=self.t_dgrad)
+                 aux_act=ops.ACT_RELU, tile=self.t_dgrad, group=grp)
 
     def _conv2_dgrad(self):
         """conv2 dgrad: whole-image LDS conv over un-pool(dP2) with flipped taps -> dP1 (ReLU'(P1)-masked)."""

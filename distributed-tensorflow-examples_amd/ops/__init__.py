@@ -185,7 +185,7 @@ def _mat(t, mode, rows, K, ld):
 def gemm(A, B, out, *, M, N, K, amode=KMAJ, lda=None, bmode=KMAJ, ldb=None, ldc=None, bias=None, bias_axis=0,
          act=ACT_NONE, alpha=1.0, beta=0.0, atomic=False, splits=1, tile=None, aux=None, ld_aux=None, aux_act=0,
          b_ones_row=-1, keep=1.0, seed=0, counter=None, pooled=None, argmax=None, PH=0, PW=0, PC=0, out2=None,
-         ldc2=0, out2_trans=False, bias_out=None, workspace=None, a_ones_row=-1):
+         ldc2=0, out2_trans=False, bias_out=None, workspace=None, a_ones_row=-1, group=None):
     """out[M,N] = epilogue( A(m,k) . B(n,k) ).
 
     A(m,k) = A[m*lda+k] (KMAJ) or A[k*lda+m] (RMAJ); likewise B(n,k).
@@ -196,6 +196,8 @@ def gemm(A, B, out, *, M, N, K, amode=KMAJ, lda=None, bmode=KMAJ, ldb=None, ldc=
     bias_out[n] (W[in][out] weight gradients: the bias gradient without a column-sum launch).
     splits > 1 without atomic: split-K whose last-arriving split runs the fused
     epilogue (workspace = (ws, tile_ctr), default: a per-device cached one).
+    group: a ``gemm_group`` this GEMM joins if it fits (it then leaves with the group's launch);
+    without one, or if it does not fit, it launches now.
     """
     if lda is None:
         lda = K if amode == KMAJ else M
@@ -219,7 +221,7 @@ def gemm(A, B, out, *, M, N, K, amode=KMAJ, lda=None, bmode=KMAJ, ldb=None, ldc=
         require().gemm(A, amode, lda, B, bmode, ldb, M, N, K, out, ldc, bias, bias_axis, act, alpha, beta, atomic,
                        splits, tile, aux, ld_aux, aux_act, b_ones_row, keep, seed, counter, pooled, argmax, PH, PW,
                        PC, out2, ldc2, out2_trans, bias_out, ws, ctr, a_ones_row,
-                       ones_page(out.device) if tile in GLDS_TILES else None)
+                       ones_page(out.device) if tile in GLDS_TILES else None, group)
         return out
     # CPU reference
     if a_ones_row >= 0:
@@ -637,13 +639,13 @@ def head_xent(h, w, b, labels, dz, dl, loss_sum, correct, logits=None, scale=1.0
     dz.copy_(g.to(dz.dtype))
 
 
-def head_wgrad(dl, h, dw, db, nc, scale=1.0, parts=None, loss_sum=None, correct=None):
+def head_wgrad(dl, h, dw, db, nc, scale=1.0, parts=None, loss_sum=None, correct=None, group=None):
     """Classifier-head weight / bias gradient, stored: dw[c][:K] = scale * sum_b dl[b][c] h[b][:],
     db[c] = scale * sum_b dl[b][c] (one workgroup per 8 columns over the whole batch, fixed order).
     ``parts``: head_xent's per-workgroup loss / hit partials, summed by the bias workgroup into
-    ``loss_sum`` / ``correct`` (needs ``db``)."""
+    ``loss_sum`` / ``correct`` (needs ``db``).  ``group``: a ``gemm_group`` to join (as ``gemm``)."""
     if h.is_cuda:
-        require().head_wgrad(dl, h, dw, db, nc, scale, parts, loss_sum, correct)
+        require().head_wgrad(dl, h, dw, db, nc, scale, parts, loss_sum, correct, group)
         return
     d = dl[:, :nc].float()
     dw[:, : h.shape[1]] = (scale * (d.t() @ h.float())).to(dw.dtype)
@@ -657,21 +659,26 @@ def head_wgrad(dl, h, dw, db, nc, scale=1.0, parts=None, loss_sum=None, correct=
 
 @contextlib.contextmanager
 def gemm_group(anchor):
-    """Grouped launch: the head_wgrad and glds-tile-12 one-split gemm calls inside the block are
-    recorded and leave as ONE kernel launch at its end (head weight gradient, then the
-    (KMAJ, RMAJ) and (RMAJ, RMAJ) GEMMs in recording order; any other mix launches one by one).
-    fp32 small-tile GEMMs (the GAN / autoencoder layers): a (RMAJ, RMAJ) weight gradient and a
-    (KMAJ, KMAJ) data gradient recorded in the block leave as one paired launch.
-    CPU tensors: a no-op (the ops run eagerly)."""
+    """Grouped launch: yields a group; the ``gemm`` / ``head_wgrad`` calls that pass it as ``group=``
+    join it (glds tile 12 or 22, bf16, one split; fp32 small tile; a head weight gradient - a call
+    that does not fit launches at once, as do all calls without ``group=``) and leave as ONE kernel
+    launch when the block ends: the head weight gradient, then the (KMAJ, RMAJ) and (RMAJ, RMAJ)
+    GEMMs (any other mix launches one by one, in the order added); of the small-tile GEMMs (the
+    GAN / autoencoder layers) a (RMAJ, RMAJ) weight gradient and a (KMAJ, KMAJ) data gradient as
+    one paired launch.  A block that raises launches none of its group (the calls that did not
+    join have run).  The group holds its pieces' tensors until then.
+    CPU tensors (``anchor``): yields None, the ops run eagerly."""
     if not anchor.is_cuda:
-        yield
+        yield None
         return
-    lib = require()
-    lib.gemm_group(anchor, True)
+    require()
+    grp = torch.classes.dtfe.GemmGroup()
     try:
-        yield
-    finally:
-        lib.gemm_group(anchor, False)
+        yield grp
+    except BaseException:
+        grp.clear()
+        raise
+    grp.launch()
 
 
 # --------------------------------------------------------------- optimizer

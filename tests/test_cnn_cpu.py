@@ -179,5 +179,11 @@ def test_head_loss_partials_cpu_semantics():
     dz, dl = args()
     ops.head_xent(h, w, None, labels, dz, dl, loss, corr, scale=1.0 / B, parts=parts)
     assert float(loss) == 1.0 and int(corr) == 1
-    ops.head_wgrad(dl, h, torch.empty(NC, K), torch.empty(NC), NC, parts=parts, loss_sum=loss, correct=corr)
-    assert abs(float(loss) - 1.0 - float(loss_a)) < 1e-5 and int(corr) - 1 == int(corr_a)
+    dw = torch.empty(NC, K)
+    with ops.gemm_group(h) as grp:   # CPU tensors: no group, the ops run eagerly
+        assert grp is None
+        ops.head_wgrad(dl, h, dw, torch.empty(NC), NC, parts=parts, loss_sum=loss, correct=corr, group=grp)
+        assert abs(float(loss) - 1.0 - float(loss_a)) < 1e-5 and int(corr) - 1 == int(corr_a)
+        out = torch.empty(NC, K)
+        ops.gemm(dl[:, :NC].t().contiguous(), h.t().contiguous(), out, M=NC, N=K, K=B, group=grp)
+        assert torch.allclose(out, dw, atol=1e-6)

@@ -114,12 +114,18 @@ def test_fc_tile22_layouts(modes, N, splits):
     assert (out[:, N:] == 123.0).all()  # nothing stored past N
 
 
-@pytest.mark.parametrize("tile", [12, 22])
-def test_gemm_group_matches_separate_launches(tile):
-    """ops.gemm_group: the head weight gradient + fc1 data gradient + fc1 weight gradient recorded
-    and launched as ONE grid give bitwise the results of the separate launches (tile 22: the group's
-    per-wave head body sums in another order than head_wgrad's kernel - head compared to 1e-5)."""
-    B_, K1, FC, NC = 1024, 3136, 1024, 10
+@pytest.mark.parametrize("tile,B_,FC,K1", [
+    pytest.param(12, 1024, 1024, 3136, id="12"), pytest.param(22, 1024, 1024, 3136, id="22"),  # the MNIST CNN's
+    # one 64-row tile of the weight gradient; the head's 64 / 4 + 1 = 17 workgroups pad to 24
+    pytest.param(12, 128, 64, 192, id="12-small"),
+    # the last n-tile (8 real columns) clamps its source columns
+    pytest.param(22, 256, 256, 136, id="22-small")])
+def test_gemm_group_matches_separate_launches(tile, B_, FC, K1):
+    """ops.gemm_group: the head weight gradient + fc1 data gradient + fc1 weight gradient added to a
+    group and launched as ONE grid give bitwise the results of the separate launches (tile 22: the group's
+    per-wave head body sums in another order than head_wgrad's kernel - head compared to 1e-5).
+    Column K1 of the weight gradient's N = K1 + 1 is the ones column (the bias gradient)."""
+    NC = 10
     g = torch.Generator(device="cuda").manual_seed(3)
     dz = torch.randn(B_, FC, device="cuda", generator=g).to(bf)
     w1 = (torch.randn(FC, K1, device="cuda", generator=g) * 0.02).to(bf)
@@ -135,11 +141,14 @@ def test_gemm_group_matches_separate_launches(tile):
         hw = torch.full((NC, FC), float("nan"), device="cuda")
         hb = torch.full((NC,), float("nan"), device="cuda")
         ctx = ops.gemm_group(dz) if grouped else __import__("contextlib").nullcontext()
-        with ctx:
-            ops.head_wgrad(dl, h, hw, hb, NC)
-            ops.gemm(dz, w1, dp2, M=B_, N=K1, K=FC, bmode=ops.RMAJ, ldb=K1, aux=p2, aux_act=ops.ACT_RELU, tile=tile)
+        with ctx as grp:
+            ops.head_wgrad(dl, h, hw, hb, NC, group=grp)
+            ops.gemm(dz, w1, dp2, M=B_, N=K1, K=FC, bmode=ops.RMAJ, ldb=K1, aux=p2, aux_act=ops.ACT_RELU, tile=tile,
+                     group=grp)
             ops.gemm(dz, p2, gw, M=FC, N=K1 + 1, K=B_, amode=ops.RMAJ, lda=FC, bmode=ops.RMAJ, ldb=K1, ldc=K1,
-                     b_ones_row=K1, bias_out=gb, tile=tile)
+                     b_ones_row=K1, bias_out=gb, tile=tile, group=grp)
+            if grouped:  # all three joined: a shape that fell back to separate launches must not pass
+                assert grp.pieces() == 3
         torch.cuda.synchronize()
         return dp2, gw, gb, hw, hb
 
@@ -154,3 +163,34 @@ def test_gemm_group_matches_separate_launches(tile):
     assert (grp[3] - hw_ref).abs().max().item() < 1e-4 * hw_ref.abs().max().item() + 1e-6
     ref = (dz.float() @ w1.float()) * (p2.float() > 0)
     assert (grp[0].float() - ref).abs().max().item() < 1e-2 * ref.abs().max().item()
+
+
+def test_gemm_group_is_explicit():
+    """Only the calls that name the group join it, a block that raises launches none of its group, and
+    nothing of the group outlives the block; a group reports its pieces until it launches them."""
+    M, N, K = 128, 128, 64
+    g = torch.Generator(device="cuda").manual_seed(4)
+    A = torch.randn(M, K, device="cuda", generator=g).to(bf)
+    Bm = torch.randn(N, K, device="cuda", generator=g).to(bf)
+    out = [torch.full((M, N), float("nan"), device="cuda") for _ in range(5)]
+    with pytest.raises(RuntimeError, match="stop"):
+        with ops.gemm_group(A) as grp:
+            ops.gemm(A, Bm, out[0], M=M, N=N, K=K, tile=12)              # eligible, but not named: launches now
+            ops.gemm(A, Bm, out[1], M=M, N=N, K=K, tile=12, group=grp)
+            assert grp.pieces() == 1
+            raise RuntimeError("stop")
+    assert grp.pieces() == 0
+    ops.gemm(A, Bm, out[2], M=M, N=N, K=K, tile=12)                      # the thread is back to plain launches
+    torch.cuda.synchronize()
+    assert not torch.isnan(out[0]).any() and torch.isnan(out[1]).all() and torch.equal(out[0], out[2])
+    ref = A.float() @ Bm.float().t()
+    assert (out[0] - ref).abs().max().item() < 1e-5 * ref.abs().max().item()
+    with ops.gemm_group(A) as grp:
+        ops.gemm(A, Bm, out[3], M=M, N=N, K=K, tile=12, group=grp)
+        ops.gemm(A, Bm, out[4], M=M, N=N, K=K, tile=12, group=grp)
+        assert grp.pieces() == 2
+        torch.cuda.synchronize()
+        assert torch.isnan(out[3]).all() and torch.isnan(out[4]).all()   # held until the block ends
+    assert grp.pieces() == 0
+    torch.cuda.synchronize()
+    assert torch.equal(out[3], out[0]) and torch.equal(out[4], out[0])

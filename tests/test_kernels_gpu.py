@@ -3,6 +3,7 @@
 Asymmetric operands everywhere (A=I checks with asymmetric B catch C-write
 transposes), odd sizes for masked tails, all operand layouts.
 """
+import contextlib
 import itertools
 
 import pytest
@@ -81,6 +82,43 @@ def test_gemm_small_tile_ones_rows_and_aux():
     ops.gemm(X, W, g, M=256, N=64, K=100, aux=y, aux_act=ops.ACT_SIGMOID, tile=ops.TILE_SMALL)
     exp = (X.cpu() @ W.cpu().t()) * y.cpu() * (1 - y.cpu())
     assert _rel(g.cpu(), exp) < 1e-5
+
+
+@pytest.mark.parametrize("n_in,n_out,rows_w,rows_d,pad,bitwise", [
+    (40, 24, 37, 37, 1, True),      # row strides 41 / 25: no 16-B operand loads (6 + 9 tiles)
+    (64, 32, 48, 48, 0, True),      # row strides 64 / 32: the KMAJ operands load 16 B at a time (10 + 12 tiles)
+    (208, 240, 64, 128, 0, False)])  # 210 + 104 tiles: the pair splits K 8 ways, each piece alone 16 ways
+def test_gemm_small_pair_matches_separate_launches(n_in, n_out, rows_w, rows_d, pad, bitwise):
+    """A small fp32 layer's weight gradient ((RMAJ, RMAJ), bias gradient through A's ones row) and a data
+    gradient ((KMAJ, KMAJ), act'(aux) epilogue) joined in one gemm_group - one paired launch - against
+    the two separate launches: bitwise where every grid, paired or not, stays below 256 tiles (the same
+    16-way K split); across that threshold both against an fp64 reference at the 1e-5 of
+    test_gemm_small_tile_exact_fp32."""
+    torch.manual_seed(21)
+    x, dz = torch.randn(rows_w, n_in + pad), torch.randn(rows_w, n_out + pad)
+    dz2, w = torch.randn(rows_d, n_out + pad), torch.randn(n_in, n_out + pad)
+    y = torch.sigmoid(torch.randn(rows_d, n_in))
+    ref = (x[:, :n_in].double().t() @ dz[:, :n_out].double(), dz[:, :n_out].double().sum(0),
+           (dz2[:, :n_out].double() @ w[:, :n_out].double().t()) * (y * (1 - y)).double())
+    x, dz, dz2, w, y = (t.to(DEV) for t in (x, dz, dz2, w, y))
+
+    def run(grouped):
+        gw, gb, dx = (torch.full(s, float("nan"), device=DEV) for s in ((n_in, n_out), (n_out,), (rows_d, n_in)))
+        with ops.gemm_group(x) if grouped else contextlib.nullcontext() as grp:
+            ops.gemm(x, dz, gw, M=n_in + 1, N=n_out, K=rows_w, amode=ops.RMAJ, lda=n_in + pad, bmode=ops.RMAJ,
+                     ldb=n_out + pad, a_ones_row=n_in, bias_out=gb, tile=ops.TILE_SMALL, group=grp)
+            ops.gemm(dz2, w, dx, M=rows_d, N=n_in, K=n_out, lda=n_out + pad, ldb=n_out + pad, aux=y,
+                     aux_act=ops.ACT_SIGMOID, tile=ops.TILE_SMALL, group=grp)
+            assert not grouped or grp.pieces() == 2
+        torch.cuda.synchronize()
+        return [t.cpu() for t in (gw, gb, dx)]
+
+    sep, grp = run(False), run(True)
+    for s, g, r in zip(sep, grp, ref):
+        assert not torch.isnan(s).any() and not torch.isnan(g).any()
+        assert _rel(s.double(), r) < 1e-5 and _rel(g.double(), r) < 1e-5
+        if bitwise:
+            assert torch.equal(s, g)
 
 
 def test_gemm_identity_asymmetric():
@@ -338,8 +376,8 @@ def test_head_loss_partials_fold(B, grouped):
         ops.head_xent(h, w, b, labels, dz, dl, loss, corr, scale=1.0 / B, parts=parts)
         assert float(loss) == 3.0 and int(corr) == 5   # untouched until the fold
         if grouped:
-            with ops.gemm_group(dz):
-                ops.head_wgrad(dl, h, dw, db, NC, parts=parts, loss_sum=loss, correct=corr)
+            with ops.gemm_group(dz) as grp:
+                ops.head_wgrad(dl, h, dw, db, NC, parts=parts, loss_sum=loss, correct=corr, group=grp)
         else:
             ops.head_wgrad(dl, h, dw, db, NC, parts=parts, loss_sum=loss, correct=corr)
         outs.append((loss.clone(), corr.clone()))
