@@ -271,22 +271,32 @@ class MnistCnnTrainer:
     # ------------------------------------------------------------------
     def forward(self, keep=None, logits=None):
         """conv1 (+ the fused batch sampling in standalone mode), conv2, fc1 (+dropout), head.
-        ``keep=1.0`` and a ``logits`` buffer: the evaluation forward (no dropout)."""
+        ``keep=1.0`` and a ``logits`` buffer: the evaluation forward (no dropout).
+
+        The random streams' contract (``data_ctr`` = c; both streams are the counter-based hash of
+        csrc/kernels/common.h, host mirror ``ops.hash_u32`` / ``ops.hash_uniform``):
+
+          * standalone (own dataset, this class and the fp32 one, fused or separate gather): training
+            step s = 0, 1, ... starts with c = s.  Sampling reads c: image b is row
+            ``hash_u32(seed + 1, c * B + b) % n_rows``.  fc1's dropout reads the same c: element
+            (row, col) of h is kept where ``hash_uniform(seed + 2, c * B*FC + row * FC + col) <
+            float32(keep)``.  The head, the last reader, then advances c by one - once per forward.
+          * batches fed by the caller (``CnnProgram``): nothing in the forward advances c.
+            ``CnnProgram.load_batch`` advances it before the forward, so the k-th loaded batch
+            (k = 1, 2, ...) has its dropout mask at c = k; ``evaluate`` restores c."""
         B = self.B
         keep = self.keep if keep is None else keep
-        fused = False
         if self.data is not None and self.device.type == "cuda" and B >= 256 and self.fused_gather:
-            # standalone: batch sampling (advances data_ctr), accumulator clearing and conv1 in ONE launch
+            # standalone: batch sampling, accumulator clearing and conv1 in ONE launch
             # (the sampling counter is advanced by head_xent, after its last reader: fc1's dropout -
             # a grid-wide last-arriver atomic here serialised ~10 us of the launch)
             ops.require().conv1_gather_fwd(self.data.images, self.data.labels, self.seed + 1, self.data_ctr,
                                            self.no_done, self.labels, self.x, self.w["wc1"], self.b["bc1"],
                                            self.p1, self.a1, self.accum)
-            fused = True
         else:
-            if self.data is not None:  # sample the batch on device (advances data_ctr) and clear
+            if self.data is not None:  # sample the batch on device and clear (done=None: the head advances data_ctr)
                 ops.gather_rows(self.data.images, self.x.view(B, -1), None, self.data.labels, self.labels,
-                                seed=self.seed + 1, counter=self.data_ctr, done=self.data_done, zero=self.accum)
+                                seed=self.seed + 1, counter=self.data_ctr, done=None, zero=self.accum)
             else:
                 for t in self.accum:
                     t.zero_()
@@ -299,7 +309,7 @@ class MnistCnnTrainer:
                  keep=keep, seed=self.seed + 2, counter=self.data_ctr, tile=self.t_fwd)
         ops.head_xent(self.h, self.w["out"], self.b["bout"], self.labels, self.dzf, self.dl, self.loss_sum,
                       self.correct, logits, scale=1.0 / B, inv_keep=1.0 / keep,
-                      step_counter=self.data_ctr if fused else None,
+                      step_counter=self.data_ctr if self.data is not None else None,
                       parts=self.head_parts)
 
     def forward_backward(self):
@@ -510,12 +520,14 @@ class MnistCnnF32Trainer(MnistCnnTrainer):
 
     def forward(self, keep=None, logits=None, advance=False):
         """``advance``: the training step's forward - the fused head also advances the dropout /
-        sampling counter (forward_backward's call)."""
+        sampling counter (forward_backward's call).  The streams follow MnistCnnTrainer.forward's
+        contract: sampling and dropout of step s both read counter value s, and the counter advances
+        ONCE per training step, after both (the gather does not advance it)."""
         B, K1 = self.B, 7 * 7 * C2
         keep = self.keep if keep is None else keep
         if self.data is not None:
             ops.gather_rows(self.data.images, self.x.view(B, -1), None, self.data.labels, self.labels,
-                            seed=self.seed + 1, counter=self.data_ctr, done=self.data_done, zero=self.accum)
+                            seed=self.seed + 1, counter=self.data_ctr, done=None, zero=self.accum)
         else:
             for t in self.accum:
                 t.zero_()
@@ -617,7 +629,7 @@ class CnnProgram(StepProgram):
         c.x.copy_(x.reshape(B, IMG, IMG, 1).to(c.x.dtype))  # bf16 or fp32 (--dtype)
         lab = y.reshape(B, -1)
         c.labels.copy_((lab.argmax(1) if lab.shape[1] > 1 else lab[:, 0]).to(c.labels.dtype))
-        c.data_ctr += 1  # dropout stream position (the HBM gather advances it in standalone mode)
+        c.data_ctr += 1  # dropout stream position: batch k reads k (MnistCnnTrainer.forward's contract)
 
     def compute_grads(self):
         self.core.forward_backward()

@@ -26,7 +26,7 @@ __all__ = [
     "OPT_MOMENTUM", "OPT_ADAM", "OPT_RMSPROP", "available", "load", "require", "pick_tile", "split_workspace",
     "TILE_DIMS", "FC_TILE", "TILE_SMALL", "GEMM_KTILE", "GLDS_TILES", "glds_ok", "ones_page", "bn_stats", "bn_apply", "bn_bwd_stats",
     "bn_bwd_apply", "relu_bits", "shortcut_grad_add",
-    "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_uniform",
+    "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal",
 ]
@@ -139,16 +139,32 @@ def pick_tile(M: int, N: int) -> int:
 
 
 # --------------------------------------------------------------- references
-def hash_uniform(seed, idx):
-    """Host mirror of the kernels' counter-based RNG (common.h hash_u32/hash_uniform):
-    splitmix-style 64-bit mix of (seed, element index) -> uniform [0, 1) with 24 bits."""
+def hash_u32(seed, idx):
+    """Host mirror of the kernels' counter-based RNG (common.h hash_u32): splitmix-style 64-bit mix
+    of (seed, element index), low 32 bits, as a numpy uint32 (array-shaped like ``idx``).  Batch
+    sampling takes it modulo the row count: row(b) = hash_u32(seed, step * B + b) % n_rows."""
     with np.errstate(over="ignore"):
-        z = (np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15) + np.asarray(idx, dtype=np.uint64)
-             * np.uint64(0xD1B54A32D192ED03) + np.uint64(0x632BE59BD9B4E019))
+        z = (np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) * np.uint64(0x9E3779B97F4A7C15)
+             + np.asarray(idx, dtype=np.uint64) * np.uint64(0xD1B54A32D192ED03) + np.uint64(0x632BE59BD9B4E019))
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z ^= z >> np.uint64(31)
-    return ((z & np.uint64(0xFFFFFFFF)) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+        z = z ^ (z >> np.uint64(31))
+    return (z & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def hash_uniform(seed, idx):
+    """Host mirror of common.h hash_uniform: the top 24 bits of hash_u32 -> fp32 uniform [0, 1)."""
+    return (hash_u32(seed, idx) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def _dropout_ref(x, idx, keep, seed, base):
+    """The kernels' dropout on the CPU: element with stream index ``base + idx`` is kept where its
+    fp32 uniform is < float32(keep), and scaled by the fp32 reciprocal 1.f / keep (fp32 product)."""
+    k = np.float32(keep)
+    u = hash_uniform(seed, np.asarray(idx, dtype=np.uint64).reshape(-1) + np.uint64(base))
+    kept = torch.from_numpy(u < k).reshape(x.shape)
+    inv = torch.tensor(float(np.float32(1.0) / k), dtype=torch.float32)
+    return torch.where(kept, x.float() * inv, torch.zeros_like(x, dtype=torch.float32))
 
 
 def _act_ref(x, act):
@@ -262,8 +278,7 @@ def gemm(A, B, out, *, M, N, K, amode=KMAJ, lda=None, bmode=KMAJ, ldb=None, ldc=
     if keep < 1.0:
         step = int(counter.reshape(-1)[0].item()) if counter is not None else 0
         oidx0 = torch.arange(M).unsqueeze(1) * ldc + torch.arange(N).unsqueeze(0)
-        u = hash_uniform(seed, oidx0.reshape(-1).numpy().astype(np.uint64) + np.uint64(step * M * N))
-        x = torch.where(torch.from_numpy(u).reshape(M, N) < keep, x / keep, torch.zeros_like(x))
+        x = _dropout_ref(x, oidx0.numpy(), keep, seed, step * M * N)
     if aux is not None:
         aidx = torch.arange(M).unsqueeze(1) * ld_aux + torch.arange(N).unsqueeze(0)
         x = x * _act_grad_from_out_ref(aux.reshape(-1).float()[aidx], aux_act)
@@ -932,8 +947,11 @@ def bias_act(x, bias, out, act, keep=1.0, seed=0, counter=None):
     if x.is_cuda:
         require().bias_act(x, bias, out, act, keep, seed, counter)
         return
-    v = x.float() + (bias.float() if bias is not None else 0)
-    out.copy_(_act_ref(v, act).to(out.dtype))
+    v = _act_ref(x.float() + (bias.float() if bias is not None else 0), act)
+    if keep < 1.0:  # bias_act_kernel: stream index step * M*N + i over the flat [M][N] tensor
+        step = int(counter.reshape(-1)[0].item()) if counter is not None else 0
+        v = _dropout_ref(v, np.arange(v.numel()), keep, seed, step * v.numel())
+    out.copy_(v.to(out.dtype))
 
 
 # -------------------------------------------------------------------- LSTM

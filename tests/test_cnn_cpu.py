@@ -1,6 +1,7 @@
 """MNIST CNN program on CPU (the fp32 PyTorch reference path of every op): the --dtype fp32 step
 against fp32 autograd, evaluation (the Test-Accuracy line), the data-parallel launch order, and
 the --dtype / --bucket_mb flag routing."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -17,8 +18,10 @@ def _batch(n, seed=0):
     return x, y
 
 
-def autograd_f32(core):
-    """fp32 autograd of the CNN on the program's own parameters and staged batch (dropout off)."""
+def autograd_f32(core, mask=None, keep=1.0, pre_out=None):
+    """fp32 autograd of the CNN on the program's own parameters and staged batch (dropout off, or
+    with ``mask`` - [B][FC] bool, the host mirror's dropout mask: h = relu(pre) * mask *
+    float32(1 / keep)); ``pre_out`` (list): receives fc1's pre-activation."""
     P, n = core.P, core.names
 
     def v(k):
@@ -28,7 +31,12 @@ def autograd_f32(core):
     x = core.x.float().permute(0, 3, 1, 2)
     z = F.max_pool2d(F.relu(F.conv2d(x, wc1.permute(0, 3, 1, 2), bc1, padding=2)), 2)
     z = F.max_pool2d(F.relu(F.conv2d(z, wc2.permute(0, 3, 1, 2), bc2, padding=2)), 2)
-    h = F.relu(z.permute(0, 2, 3, 1).reshape(x.shape[0], -1) @ wd1.t() + bd1)
+    pre = z.permute(0, 2, 3, 1).reshape(x.shape[0], -1) @ wd1.t() + bd1
+    if pre_out is not None:
+        pre_out.append(pre.detach())
+    h = F.relu(pre)
+    if mask is not None:
+        h = h * mask.float() * float(np.float32(1.0) / np.float32(keep))
     logits = h @ wo.t() + bo
     loss = F.cross_entropy(logits, core.labels.long())
     loss.backward()

@@ -1,7 +1,10 @@
 """End-to-end numerics of the fused MNIST-CNN step program vs torch autograd (fp32)."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from dtfe import ops
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +24,9 @@ class _Bf16Point(torch.autograd.Function):
 q = _Bf16Point.apply
 
 
-def _reference_grads(trainer):
+def _reference_grads(trainer, mask=None, keep=1.0, pre_out=None):
+    """``mask`` ([B][FC] bool, the host mirror's dropout mask): h = relu(pre) * mask * float32(1 / keep),
+    rounded once as the fc1 epilogue does; ``pre_out`` (list): receives fc1's pre-activation."""
     P, n = trainer.P, trainer.names
     x = trainer.x.float().permute(0, 3, 1, 2).cpu()            # what the kernels consumed
     y = trainer.labels.long().cpu()
@@ -40,7 +45,13 @@ def _reference_grads(trainer):
     z = F.conv2d(z, wc2.permute(0, 3, 1, 2), bc2, padding=2)
     z = q(F.max_pool2d(F.relu(z), 2))
     z = z.permute(0, 2, 3, 1).reshape(x.shape[0], -1)           # NHWC flatten, as the kernels
-    h = F.relu(q(z @ wd1.t() + bd1))
+    pre = z @ wd1.t() + bd1
+    if pre_out is not None:
+        pre_out.append(pre.detach())
+    if mask is None:
+        h = F.relu(q(pre))
+    else:
+        h = q(F.relu(pre) * mask.float() * float(np.float32(1.0) / np.float32(keep)))
     logits = h @ wo.t() + bo
     loss = F.cross_entropy(logits, y)
     loss.backward()
@@ -321,3 +332,176 @@ def test_cnn_fp32_local_run_trains(capsys, tmp_path):
     out = capsys.readouterr().out
     assert rc == 0
     assert "Global step 4 Local step 3" in out and "Test-Accuracy: " in out, out[-2000:]
+
+
+# ---------------------------------------------------------------------------
+# dropout on (keep 0.75, the headline setting): sampled rows, dropout mask and gradients of whole
+# steps against the host mirror of the device RNG (ops.hash_u32 / ops.hash_uniform) - the contract
+# written in MnistCnnTrainer.forward's docstring
+N_IMAGES = 5000
+
+
+def _mirror_mask(seed, step, B, keep):
+    """[B][1024] bool (True = kept): fc1's dropout mask at counter value ``step``."""
+    n = B * 1024
+    u = ops.hash_uniform(seed, np.uint64(step * n) + np.arange(n, dtype=np.uint64))
+    return torch.from_numpy(u < np.float32(keep)).reshape(B, 1024)
+
+
+def _mirror_rows(seed, step, B):
+    h = ops.hash_u32(seed, np.uint64(step * B) + np.arange(B, dtype=np.uint64))
+    return torch.from_numpy((h % np.uint32(N_IMAGES)).astype(np.int64))
+
+
+def _id_dataset():
+    """5000 random images whose pixels 0 and 1 carry the row id in base 128 (exact after the / 255
+    and bf16 round trip of the gather), labels id % 10."""
+    from dtfe.models.mnist_cnn import SyntheticMnist
+
+    g = torch.Generator().manual_seed(21)
+    imgs = torch.randint(0, 256, (N_IMAGES, 784), generator=g, dtype=torch.uint8)
+    ids = torch.arange(N_IMAGES)
+    imgs[:, 0] = (ids // 128).to(torch.uint8)
+    imgs[:, 1] = (ids % 128).to(torch.uint8)
+    return SyntheticMnist(0, "cuda", images=imgs, labels=(ids % 10).to(torch.int32))
+
+
+def _sampled_ids(x):
+    b = torch.round(x.reshape(x.shape[0], -1)[:, :2].float().cpu() * 255).long()
+    return b[:, 0] * 128 + b[:, 1]
+
+
+def _f32_reference(core, mask=None, keep=1.0, pre_out=None):
+    """test_cnn_cpu.autograd_f32 on a CPU copy of a GPU fp32 trainer's parameters and batch."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_cnn_cpu import autograd_f32
+
+    cpu = type("C", (), {})()
+    cpu.P = type("P", (), {"view": staticmethod(lambda k: core.P.view(k).cpu())})()
+    cpu.names, cpu.x, cpu.labels = core.names, core.x.cpu(), core.labels.cpu()
+    loss, grads, _ = autograd_f32(cpu, mask=mask, keep=keep, pre_out=pre_out)
+    return loss, grads
+
+
+def _check_mask_on_h(h, kept, pre):
+    """h == 0 wherever the mirror drops; h != 0 wherever it keeps and the reference pre-activation
+    is clearly positive (> 1e-2 of its maximum) - a class that must hold >= 1/4 of the elements."""
+    pos = pre > 1e-2 * pre.max()
+    assert pos.float().mean().item() >= 0.25
+    h = h.float().cpu()
+    assert bool((h[~kept] == 0).all()), "kept %d elements the mirror drops" % int((h[~kept] != 0).sum())
+    assert bool((h[kept & pos] != 0).all()), "dropped %d elements the mirror keeps" % int((h[kept & pos] == 0).sum())
+
+
+def _grad_errs(tr, grads):
+    return {k: ((tr.gw[k].detach().float().cpu() - g).norm() / (g.norm() + 1e-12)).item() for k, g in grads.items()}
+
+
+@pytest.mark.parametrize("kind,B", [("bf16", 64), ("bf16", 256), ("fp32", 64)])
+def test_cnn_dropout_step_matches_mirror_and_autograd(kind, B):
+    """Three training steps at keep 0.75 (B = 64: separate gather; B = 256: sampling fused into conv1;
+    fp32 trainer): at step s the sampled rows and the dropout mask are the mirror's at counter value s,
+    the counter advances once per step, loss and all eight gradients equal autograd with the mirror's
+    mask after fc1's ReLU (the dropout-off tests' tolerances).  Negative control: the mask of the
+    neighbouring counter value misses fc1's weight gradient by more than 10x the tolerance."""
+    from dtfe.models.mnist_cnn import MnistCnnF32Trainer, MnistCnnTrainer
+
+    keep = 0.75
+    cls, ref, ltol, gtol = ((MnistCnnTrainer, _reference_grads, 2e-2, 3e-2) if kind == "bf16" else
+                            (MnistCnnF32Trainer, _f32_reference, 1e-5, 1e-4))
+    tr = cls(B, "cuda", keep_prob=keep, seed=3, data=_id_dataset())
+    if kind == "bf16":
+        assert tr.fused_gather and tr.par
+    for s in range(3):
+        assert int(tr.data_ctr.item()) == s
+        tr.P.grad.fill_(3.0)
+        tr.forward_backward()
+        torch.cuda.synchronize()
+        assert int(tr.data_ctr.item()) == s + 1, "the counter advances once per training step"
+        rows = _mirror_rows(tr.seed + 1, s, B)
+        assert torch.equal(_sampled_ids(tr.x), rows), s
+        assert torch.equal(tr.labels.cpu().long(), rows % 10), s
+        kept = _mirror_mask(tr.seed + 2, s, B, keep)
+        pre = []
+        loss_ref, grads = ref(tr, mask=kept, keep=keep, pre_out=pre)
+        _check_mask_on_h(tr.h, kept, pre[0])
+        loss = tr.loss_sum.item() / B
+        assert abs(loss - loss_ref) <= ltol * (max(1.0, abs(loss_ref)) if kind == "bf16" else abs(loss_ref)), \
+            (s, loss, loss_ref)
+        errs = _grad_errs(tr, grads)
+        assert all(e < gtol for e in errs.values()), (s, sorted(errs.items(), key=lambda kv: -kv[1]))
+    for wrong in (1, 3):   # the last step ran at counter value 2
+        _, grads = ref(tr, mask=_mirror_mask(tr.seed + 2, wrong, B, keep), keep=keep)
+        err = _grad_errs(tr, grads)["wd1"]
+        assert err > 10 * gtol, (wrong, err)
+
+
+def test_cnn_fused_sampling_matches_separate_gather_with_dropout():
+    """test_cnn_fused_sampling_conv1_matches_separate_gather at keep 0.75: the separate-gather path is
+    the fused launch's oracle with dropout on too - same batch, same dropout mask (h bitwise equal),
+    same gradients, and the same counter value after each step."""
+    from dtfe.models.mnist_cnn import MnistCnnTrainer
+
+    res = {}
+    for fused in ("1", "0"):
+        tr = MnistCnnTrainer(256, "cuda", keep_prob=0.75, seed=7)
+        tr.fused_gather = fused == "1"
+        tr.P.grad.fill_(5.0)
+        for _ in range(2):
+            tr.forward_backward()
+        torch.cuda.synchronize()
+        res[fused] = dict(x=tr.x.clone(), lab=tr.labels.clone(), p1=tr.p1.clone(), h=tr.h.clone(),
+                          g=tr.P.grad.clone(), ctr=int(tr.data_ctr.item()), loss=tr.loss_sum.clone())
+    a, b = res["1"], res["0"]
+    assert a["ctr"] == b["ctr"] == 2
+    assert torch.equal(a["x"], b["x"]) and torch.equal(a["lab"], b["lab"]) and torch.equal(a["p1"], b["p1"])
+    assert torch.equal(a["h"], b["h"])
+    assert bool((a["h"] == 0).float().mean().item() > 0.25)   # dropout is on
+    assert torch.allclose(a["g"], b["g"], rtol=1e-4, atol=1e-6)
+    assert abs(a["loss"].item() - b["loss"].item()) <= 1e-5 * abs(b["loss"].item())
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+def test_cnn_program_dropout_stream_and_evaluate(dtype):
+    """CnnProgram (batches from the caller): the k-th loaded batch (k = 1, 2, ...) has the mirror's mask
+    at counter value k, and only load_batch advances the counter; evaluate() leaves the counter
+    where it was, runs without dropout, and the next training step's mask is the one it has anyway."""
+    from dtfe.models.mnist_cnn import MnistCnnModel
+
+    B, keep = 64, 0.75
+    m = MnistCnnModel()
+    m.set_dtype(dtype)
+    prog = m.program(torch.device("cuda"), B, seed=2)
+    core = prog.core
+    assert core.keep == keep
+    ref = _reference_grads if dtype == "bf16" else _f32_reference
+    g = torch.Generator().manual_seed(8)
+
+    def batch(n):
+        x = torch.rand(n, 784, generator=g)
+        y = F.one_hot(torch.randint(0, 10, (n,), generator=g), 10).float()
+        return x.cuda(), y.cuda()
+
+    def train_step(k):
+        prog.load_batch(batch(B))
+        assert int(core.data_ctr.item()) == k
+        prog.compute_grads()
+        torch.cuda.synchronize()
+        assert int(core.data_ctr.item()) == k
+        kept = _mirror_mask(core.seed + 2, k, B, keep)
+        pre = []
+        ref(core, mask=kept, keep=keep, pre_out=pre)
+        _check_mask_on_h(core.h, kept, pre[0])
+
+    train_step(1)
+    train_step(2)
+    prog.evaluate(*batch(100))
+    torch.cuda.synchronize()
+    assert int(core.data_ctr.item()) == 2
+    pre = []
+    ref(core, pre_out=pre)                      # core.x: the last evaluation chunk; keep = 1.0 there
+    _check_mask_on_h(core.h, torch.ones(B, 1024, dtype=torch.bool), pre[0])
+    train_step(3)
