@@ -8,11 +8,12 @@ the batch (on-device copy), forward, backward, the TF1 optimizer(s) and the glob
 captured into one hipGraph, on synthetic MNIST-shaped data with the reference batch sizes
 and hyper-parameters.
 
-    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20]
+    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20] [--clip_norm C]
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -28,15 +29,15 @@ from dtfe.train import MODELS  # noqa: E402
 from dtfe.utils.graphs import MultiStepGraph  # noqa: E402
 
 
-def time_model(name, steps, warmup, graph=True, steps_per_graph=1):
+def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0):
     cls, lr = MODELS[name]
     model = cls(lr=lr)
     dev = torch.device("cuda", 0)
     B = model.default_batch
     prog = model.program(dev, B, seed=0)
     gstep = torch.zeros(1, dtype=torch.int32, device=dev)
-    opts = [Optimizer(cfg, prog.P, var_list=vl, global_step=gstep, beta_power_names=bp)
-            for cfg, vl, bp in model.opt_groups]
+    opts = [Optimizer(dataclasses.replace(cfg, clip_norm=clip_norm), prog.P, var_list=vl, global_step=gstep,
+                      beta_power_names=bp) for cfg, vl, bp in model.opt_groups]
     g = torch.Generator().manual_seed(1)
     x = torch.rand(B, 784, generator=g).to(dev)
     y = torch.nn.functional.one_hot(torch.randint(0, 10, (B,), generator=g), 10).float().to(dev)
@@ -54,8 +55,11 @@ def time_model(name, steps, warmup, graph=True, steps_per_graph=1):
     run.run(steps)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
-    return {"model": name, "batch": B, "ms_per_step": round(ms, 4), "hip_graph": run.graph is not None,
-            "steps_per_graph": run.steps, "global_step": int(gstep.item())}
+    out = {"model": name, "batch": B, "ms_per_step": round(ms, 4), "hip_graph": run.graph is not None,
+           "steps_per_graph": run.steps, "global_step": int(gstep.item())}
+    if clip_norm > 0:  # (keys only with the flag: the default line stays as it was)
+        out.update(clip_norm=clip_norm, global_norm=[round(float(o.global_norm.item()), 6) for o in opts])
+    return out
 
 
 def main():
@@ -65,10 +69,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no_graph", action="store_true")
     ap.add_argument("--steps_per_graph", type=int, default=1, help="training steps per hipGraph replay")
+    ap.add_argument("--clip_norm", type=float, default=0.0,
+                    help="clip every optimizer's gradients by global norm inside the captured step (0: off)")
     a = ap.parse_args()
+    if a.clip_norm < 0:
+        ap.error("--clip_norm must be >= 0")
     for m in a.models.split(","):
-        print(json.dumps(time_model(m, a.steps, a.warmup, graph=not a.no_graph, steps_per_graph=a.steps_per_graph)),
-              flush=True)
+        print(json.dumps(time_model(m, a.steps, a.warmup, graph=not a.no_graph, steps_per_graph=a.steps_per_graph,
+                                    clip_norm=a.clip_norm)), flush=True)
 
 
 if __name__ == "__main__":

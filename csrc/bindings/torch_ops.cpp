@@ -17,6 +17,7 @@
 #include "../kernels/gemm_dense.h"
 #include "../kernels/head.h"
 #include "../kernels/lstm_seq.h"
+#include "../kernels/gradnorm.h"
 #include "../kernels/optim.h"
 
 using at::Tensor;
@@ -641,6 +642,61 @@ dtfe::OptArgs opt_args(int64_t kind, const Tensor& p, const optional<Tensor>& g,
   return a;
 }
 
+// the device scalar of a global-norm clip (grad_sumsq's out[1:]) multiplied into gscale; null when not given
+const float* clip_scale_ptr(const optional<Tensor>& t) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  check_cuda(*t, "clip_scale");
+  TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= 1, "apply_gradients: clip_scale is a float32 scalar");
+  return t->data_ptr<float>();
+}
+
+// sum of squares of (gscale * g) over the plan's chunks -> out[0] = norm, out[1] = clip_norm / max(norm, clip_norm).
+// plan: int64 [nchunk, 2] device table of (offset, count <= 8192) (ops.grad_norm_plan); partials: fp32 [>= nchunk];
+// ticket: zeroed int32 [1] (the kernel resets it); max_blocks: 0 = default grid (a test forces 1)
+void grad_sumsq(const optional<Tensor>& g, const optional<Tensor>& g16, double gscale, double clip_norm,
+                const Tensor& plan, const Tensor& partials, const Tensor& ticket, const Tensor& out,
+                int64_t max_blocks) {
+  check_cuda(plan, "plan"); check_cuda(partials, "partials"); check_cuda(ticket, "ticket"); check_cuda(out, "out");
+  dtfe::GradNormArgs a{};
+  if (g.has_value() && g->defined()) {
+    check_cuda(*g, "g");
+    TORCH_CHECK(g->scalar_type() == at::kFloat && g->is_contiguous(), "grad_sumsq: g is contiguous float32");
+    a.g = g->data_ptr<float>();
+  }
+  if (g16.has_value() && g16->defined()) {
+    check_cuda(*g16, "g16");
+    TORCH_CHECK(g16->scalar_type() == at::kBFloat16 && g16->is_contiguous(), "grad_sumsq: g16 is contiguous bfloat16");
+    a.g16 = reinterpret_cast<const dtfe::bf16*>(g16->data_ptr());
+  }
+  TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "grad_sumsq: exactly one of g / g16");
+  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 2,
+              "grad_sumsq: plan is a contiguous int64 [nchunk, 2] table");
+  static_assert(sizeof(dtfe::GradChunk) == 2 * sizeof(int64_t), "plan rows are GradChunk");
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.numel() >= plan.size(0),
+              "grad_sumsq: one float32 partial per chunk");
+  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "grad_sumsq: int32 ticket");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= 2, "grad_sumsq: float32 out[2]");
+  TORCH_CHECK(clip_norm >= 0 && max_blocks >= 0, "grad_sumsq: clip_norm and max_blocks are >= 0");
+  a.gscale = (float)gscale; a.clip_norm = (float)clip_norm;
+  a.plan = reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()); a.nchunk = (int)plan.size(0);
+  a.partials = partials.data_ptr<float>();
+  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
+  a.out = out.data_ptr<float>();
+  a.max_blocks = (int)max_blocks;
+  dtfe::launch_grad_sumsq(a, cur_stream());
+}
+
+// t[i] *= scale[0] over the plan's chunks (same table as grad_sumsq's)
+void scale_(const Tensor& t, const Tensor& scale, const Tensor& plan) {
+  check_cuda(t, "t"); check_cuda(scale, "scale"); check_cuda(plan, "plan");
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous(), "scale_: contiguous float32 tensor");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() >= 1, "scale_: float32 scalar");
+  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 2,
+              "scale_: plan is a contiguous int64 [nchunk, 2] table");
+  dtfe::launch_scale_ranges(t.data_ptr<float>(), scale.data_ptr<float>(),
+                            reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()), (int)plan.size(0), cur_stream());
+}
+
 // wait_done / wait_seen / wait_segs: this launch's items of the segments in the bit mask wait on the
 // device-side counter pair (OptArgs::wait_done / wait_seen) - a gradient produced on another stream with
 // no graph edge to the optimizer launch (the CNN's conv2 weight-gradient branch)
@@ -649,7 +705,7 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
                      double beta2, double eps, double momentum, double rho, const optional<Tensor>& beta_pow,
                      const optional<Tensor>& global_step, int64_t gs_inc, const Tensor& done, const Tensor& blob,
                      int64_t nseg, int64_t nwork, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
-                     int64_t wait_segs) {
+                     int64_t wait_segs, const optional<Tensor>& clip_scale) {
   const double hyper[6] = {lr, beta1, beta2, eps, momentum, rho};
   dtfe::OptArgs a = opt_args(kind, p, g, g16, gscale, s1, s2, hyper, beta_pow, global_step, gs_inc, done, blob, nseg,
                              nwork);
@@ -665,6 +721,7 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
     a.wait_done = wait_done->data_ptr<int>(); a.wait_seen = wait_seen->data_ptr<int>();
     a.wait_segs = (uint32_t)wait_segs;
   }
+  a.clip_scale = clip_scale_ptr(clip_scale);
   dtfe::launch_apply_gradients(a, cur_stream());
 }
 
@@ -675,16 +732,20 @@ void apply_gradients_group(int64_t kind, const Tensor& p, const optional<Tensor>
                            const c10::List<optional<Tensor>>& s2, at::ArrayRef<double> hyper,
                            const c10::List<optional<Tensor>>& beta_pow,
                            const c10::List<optional<Tensor>>& global_step, at::IntArrayRef gs_inc,
-                           at::TensorList done, at::TensorList blob, at::IntArrayRef nseg, at::IntArrayRef nwork) {
+                           at::TensorList done, at::TensorList blob, at::IntArrayRef nseg, at::IntArrayRef nwork,
+                           const optional<c10::List<optional<Tensor>>>& clip_scale) {
   const size_t n = done.size();
   TORCH_CHECK(n >= 1 && n <= (size_t)dtfe::OPT_GROUP_MAX, "apply_gradients_group: 1..4 optimizers");
   TORCH_CHECK(s1.size() == n && s2.size() == n && hyper.size() == 6 * n && beta_pow.size() == n &&
                   global_step.size() == n && gs_inc.size() == n && blob.size() == n && nseg.size() == n &&
-                  nwork.size() == n, "apply_gradients_group: one entry per optimizer in every list");
+                  nwork.size() == n && (!clip_scale.has_value() || clip_scale->size() == n),
+              "apply_gradients_group: one entry per optimizer in every list");
   dtfe::OptArgs q[dtfe::OPT_GROUP_MAX];
-  for (size_t i = 0; i < n; ++i)
+  for (size_t i = 0; i < n; ++i) {
     q[i] = opt_args(kind, p, g, g16, gscale, s1.get(i), s2.get(i), hyper.data() + 6 * i, beta_pow.get(i),
                     global_step.get(i), gs_inc[i], done[i], blob[i], nseg[i], nwork[i]);
+    if (clip_scale.has_value()) q[i].clip_scale = clip_scale_ptr(clip_scale->get(i));
+  }
   dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
 }
 
@@ -1320,11 +1381,14 @@ TORCH_LIBRARY(dtfe, m) {
       "apply_gradients(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor(b!)? s1, Tensor(c!)? s2,"
       " float lr, float beta1, float beta2, float eps, float momentum, float rho, Tensor(d!)? beta_pow,"
       " Tensor(e!)? global_step, int gs_inc, Tensor(f!) done, Tensor blob, int nseg, int nwork,"
-      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0) -> ()");
+      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0, Tensor? clip_scale=None) -> ()");
   m.def(
       "apply_gradients_group(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor?[] s1, Tensor?[] s2,"
       " float[] hyper, Tensor?[] beta_pow, Tensor?[] global_step, int[] gs_inc, Tensor[] done, Tensor[] blob,"
-      " int[] nseg, int[] nwork) -> ()");
+      " int[] nseg, int[] nwork, Tensor?[]? clip_scale=None) -> ()");
+  m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
+        " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
+  m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
   m.def("wgrad_tallk(Tensor A, int lda, Tensor B, int ldb, int M, int N, int K, Tensor(a!) out, int ldc,"
         " Tensor(b!)? bias, Tensor(c!) ws, int splits, float scale) -> ()");
   m.def("seq_stage(Tensor x, Tensor(a!) xh, int T, int I, Tensor ysrc, Tensor(b!) ydst, Tensor(c!)[] zero) -> ()");
@@ -1381,6 +1445,8 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("head_wgrad", &head_wgrad);
   m.impl("apply_gradients", &apply_gradients);
   m.impl("apply_gradients_group", &apply_gradients_group);
+  m.impl("grad_sumsq", &grad_sumsq);
+  m.impl("scale_", &scale_);
   m.impl("gather_rows", &gather_rows);
   m.impl("seq_stage", &seq_stage);
   m.impl("wgrad_tallk", &wgrad_tallk);

@@ -56,6 +56,9 @@ struct OptArgs {
   // launch): the work items of segments in wait_segs wait until *wait_done exceeds *wait_seen (set by
   // epoch_signal_kernel after the producer); the last workgroup then advances *wait_seen
   const int* wait_done; int* wait_seen; uint32_t wait_segs;
+  // optional device scalar multiplied into gscale (nullable): the scale of a global-norm clip
+  // (gradnorm.h, launch_grad_sumsq's out[1]).  Null: the arithmetic is exactly gscale's
+  const float* clip_scale;
 };
 // points a.segs / a.work into a plan blob of nseg segments
 inline void opt_blob_plan(const void* blob, size_t nseg, OptArgs& a) {

@@ -52,8 +52,8 @@ __device__ __forceinline__ float update_one(const OptArgs& a, float lr_t, long i
 }
 
 template <bool G16>
-__device__ __forceinline__ float load_grad(const OptArgs& a, long i) {
-  return (G16 ? bf2f(a.g16[i]) : a.g[i]) * a.gscale;
+__device__ __forceinline__ float load_grad(const OptArgs& a, float gs, long i) {
+  return (G16 ? bf2f(a.g16[i]) : a.g[i]) * gs;
 }
 
 // the updated values' extra destinations: bf16 copies (w16, the ps reply's w16b) and the fp32 copy pb
@@ -67,7 +67,7 @@ __device__ __forceinline__ void store_copies(const f32x4_t& p, bf16* w16, bf16* 
 }
 
 template <int KIND, bool G16>
-__device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, long i, bf16* w16, bf16* w16b, float* pb) {
+__device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, float gs, long i, bf16* w16, bf16* w16b, float* pb) {
   f32x4_t g;
   if constexpr (!G16) {
     g = *reinterpret_cast<const f32x4_t*>(a.g + i);
@@ -83,7 +83,7 @@ __device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, long i
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float x1 = s1[j], x2 = s2[j];
-    p[j] = upd<KIND>(a, lr_t, p[j], g[j] * a.gscale, x1, x2);
+    p[j] = upd<KIND>(a, lr_t, p[j], g[j] * gs, x1, x2);
     s1[j] = x1;
     s2[j] = x2;
   }
@@ -96,7 +96,7 @@ __device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, long i
 // U vec4 updates at i, i+1024, ... (one workgroup-wide stride apart): every load is issued
 // before the first update, so each thread keeps U x (3-4) 16-B loads in flight
 template <int KIND, int U, bool G16>
-__device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, long i, bf16* w16, bf16* w16b, float* pb) {
+__device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, float gs, long i, bf16* w16, bf16* w16b, float* pb) {
   f32x4_t g[U], p[U], s1[U], s2[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -119,7 +119,7 @@ __device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, long 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float x1 = s1[u][j], x2 = s2[u][j];
-      p[u][j] = upd<KIND>(a, lr_t, p[u][j], g[u][j] * a.gscale, x1, x2);
+      p[u][j] = upd<KIND>(a, lr_t, p[u][j], g[u][j] * gs, x1, x2);
       s1[u][j] = x1;
       s2[u][j] = x2;
     }
@@ -136,6 +136,9 @@ template <int KIND, bool G16>
 __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk, bf16 (&tile)[64][66]) {
   float lr_t = a.lr;
   if (KIND == OPT_ADAM) lr_t = tf1_adam_lr(a.lr, a.beta_pow);
+  // the gradient scale of this launch: the host's, times the device scalar of a global-norm clip
+  // (grad_sumsq_kernel's out[1], written by the launch before this one on the stream)
+  const float gs = a.clip_scale ? a.gscale * *a.clip_scale : a.gscale;
   bool waited = false;
   for (int wi = bid; wi < a.nwork; wi += nblk) {
     const OptWork w = a.work[wi];
@@ -162,12 +165,12 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
       auto at16 = [&](bf16* q, long jj) { return q ? q + w.start + jj : nullptr; };
       auto at32 = [&](float* q, long jj) { return q ? q + w.start + jj : nullptr; };
       for (; j + 3 * 1024 < n4; j += 4 * 1024)  // 4 independent vec4 updates in flight per thread
-        update_vec4x<KIND, 4, G16>(a, lr_t, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+        update_vec4x<KIND, 4, G16>(a, lr_t, gs, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
       for (; j < n4; j += 256 * 4)
-        update_vec4<KIND, G16>(a, lr_t, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+        update_vec4<KIND, G16>(a, lr_t, gs, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
       for (long j = n4 + threadIdx.x; j < w.count; j += 256) {
         const long li = w.start + j, i = sg.off + li;
-        const float v = update_one<KIND>(a, lr_t, i, load_grad<G16>(a, i));
+        const float v = update_one<KIND>(a, lr_t, i, load_grad<G16>(a, gs, i));
         if (sg.w16) sg.w16[li] = f2bf(v);
         if (sg.w16b) sg.w16b[li] = f2bf(v);
         if (sg.pb) sg.pb[li] = v;
@@ -185,7 +188,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
         // out-of-tile lanes load the segment's first element (never stored): no branches here
         const bool ok = r < sg.R && c < sg.C;
         const long i = sg.off + (ok ? ((long)r * sg.T + w.t) * sg.C + c : 0);
-        gv[u] = load_grad<G16>(a, i);
+        gv[u] = load_grad<G16>(a, gs, i);
         pv[u] = a.p[i];
         s1v[u] = KIND != OPT_SGD ? a.s1[i] : 0.f;
         s2v[u] = (KIND == OPT_ADAM || KIND == OPT_RMSPROP) ? a.s2[i] : 0.f;

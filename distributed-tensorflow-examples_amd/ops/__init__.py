@@ -28,7 +28,7 @@ __all__ = [
     "bn_bwd_apply", "relu_bits", "shortcut_grad_add",
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
-    "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal",
+    "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -702,12 +702,60 @@ def opt_pack(segs, work, device_like):
 
 
 def apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
-                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0):
+                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0, clip_scale=None):
     """The launch's items of the var-list segments in bit mask ``wait_segs`` wait (on the device) until
     ``wait_done`` exceeds ``wait_seen`` - a gradient produced on another stream that signals with
-    epoch_signal(wait_done) instead of a stream join; the launch's last workgroup advances ``wait_seen``."""
+    epoch_signal(wait_done) instead of a stream join; the launch's last workgroup advances ``wait_seen``.
+    ``clip_scale``: a device float32 scalar multiplied into ``gscale`` by the kernel (grad_sumsq's scale)."""
     require().apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow,
-                              global_step, gs_inc, done, blob, nseg, nwork, wait_done, wait_seen, wait_segs)
+                              global_step, gs_inc, done, blob, nseg, nwork, wait_done, wait_seen, wait_segs,
+                              clip_scale)
+
+
+GRAD_CHUNK_MAX = 8192  # csrc/kernels/gradnorm.h
+
+
+def grad_norm_plan(segs, master):
+    """The (offset, count) chunk table of a global gradient norm: ``segs`` = [(offset, numel)] of a var
+    list's variables in the flat buffer of ``master``, cut into chunks of at most GRAD_CHUNK_MAX elements
+    (a transposed variable is a flat range like any other).  The chunks cover exactly those elements:
+    no padding, no variable outside the list.  int64 [nchunk, 2] on master's device."""
+    rows = []
+    for off, n in segs:
+        off, n = int(off), int(n)
+        if off < 0 or n < 0 or off + n > master.numel():
+            raise ValueError("grad_norm_plan: segment (%d, %d) outside a buffer of %d" % (off, n, master.numel()))
+        rows += [[off + st, min(GRAD_CHUNK_MAX, n - st)] for st in range(0, n, GRAD_CHUNK_MAX)]
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(master.device)
+
+
+def _plan_cat(t, plan):
+    rows = plan.tolist()
+    return torch.cat([t[o:o + n] for o, n in rows]) if rows else t[:0]
+
+
+def grad_sumsq(g, g16, gscale, clip_norm, plan, partials, ticket, out, max_blocks=0):
+    """out[0] = sqrt(sum over the plan of (gscale * g)^2), out[1] = clip_norm / max(out[0], clip_norm) (the
+    factor of tf.clip_by_global_norm; 1 when the norm is within clip_norm).  Exactly one of ``g`` (fp32) /
+    ``g16`` (bf16).  GPU: one launch, bitwise reproducible whatever the grid (``max_blocks`` caps it, for
+    tests); ``partials`` (fp32, one per chunk) and ``ticket`` (zeroed int32) are its scratch."""
+    if out.is_cuda:
+        require().grad_sumsq(g, g16, gscale, clip_norm, plan, partials, ticket, out, max_blocks)
+        return
+    x = _plan_cat(g if g is not None else g16, plan).double() * float(np.float32(gscale))
+    norm = np.float32(math.sqrt(float((x * x).sum())))
+    c = np.float32(clip_norm)
+    out[0] = float(norm)
+    out[1] = float(c / norm) if c > 0 and norm > c else 1.0
+
+
+def scale_(t, scale, plan):
+    """t[i] *= scale[0] (a device scalar) over the chunks of ``plan`` (grad_norm_plan), in place."""
+    if t.is_cuda:
+        require().scale_(t, scale, plan)
+        return
+    for o, n in plan.tolist():
+        t[o:o + n] *= scale[0]
 
 
 # ------------------------------------------------------------- elementwise

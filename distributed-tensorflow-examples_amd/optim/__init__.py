@@ -153,11 +153,51 @@ class OptimizerConfig:
     momentum: float = 0.0
     rho: float = 0.9
     name: str = field(default="")
+    # tf.clip_by_global_norm over the optimizer's var list before the update; 0 = off (the reference)
+    clip_norm: float = 0.0
 
     def resolved_eps(self):
         if self.eps is not None:
             return self.eps
         return 1e-10 if self.kind == "rmsprop" else 1e-8
+
+
+class GlobalNormClip:
+    """``tf.clip_by_global_norm`` over a var list of a FlatParams, on the device: ``compute`` launches
+    the norm of ``gscale * grad`` over exactly the var list's elements into ``out = [norm, scale]``
+    with ``scale = clip_norm / max(norm, clip_norm)``.  An ``Optimizer`` with ``clip_norm`` owns one
+    and hands ``out[1:]`` to its fused apply; a ps worker owns one per optimizer group and scales its
+    gradient in place (``scale_grad``) before the push.  Stateless: nothing to checkpoint."""
+
+    def __init__(self, params: FlatParams, var_list, clip_norm: float):
+        if not clip_norm > 0:
+            raise ValueError("GlobalNormClip: clip_norm must be > 0, got %r" % (clip_norm,))
+        self.P = params
+        self.clip_norm = float(clip_norm)
+        dev = params.device
+        self.plan = ops.grad_norm_plan([(params.offsets[n], params.spec(n).numel) for n in var_list], params.master)
+        self.partials = torch.zeros(max(1, self.plan.shape[0]), dtype=torch.float32, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+
+    def compute(self, grad=None, grad16=None, gscale: float = 1.0, max_blocks: int = 0):
+        """Launch the norm on the current stream; returns the scale as a 1-element device tensor.
+        (``max_blocks``: test hook, caps the grid.)"""
+        if grad is None and grad16 is None:
+            grad = self.P.grad
+        if (grad if grad is not None else grad16).numel() < self.P.total:
+            raise ValueError("GlobalNormClip: the gradient is shorter than the flat parameter buffer")
+        ops.grad_sumsq(grad, grad16, gscale, self.clip_norm, self.plan, self.partials, self.ticket, self.out,
+                       max_blocks)
+        return self.out[1:]
+
+    def scale_grad(self, grad=None):
+        """grad[var list] *= scale, in place (after ``compute``)."""
+        ops.scale_(self.P.grad if grad is None else grad, self.out[1:], self.plan)
+
+    @property
+    def norm(self):
+        return self.out[:1]
 
 
 class Optimizer:
@@ -195,6 +235,12 @@ class Optimizer:
         self._blob = None
         if self.device.type == "cuda":
             self._build_plan()
+        # global-norm clipping (cfg.clip_norm > 0): the norm kernel's chunk plan, scratch and its two
+        # results clip_out = [norm, scale]; the apply reads the scale from the device.  No state to save.
+        self.clip_norm = float(getattr(cfg, "clip_norm", 0.0) or 0.0)
+        if self.clip_norm < 0:
+            raise ValueError("clip_norm must be >= 0 (0 = no clipping), got %r" % (cfg.clip_norm,))
+        self.clip = GlobalNormClip(params, self.var_list, self.clip_norm) if self.clip_norm > 0 else None
 
     # ---- plan of work items for the fused kernel
     def _build_plan(self, chunk: int = 0):
@@ -244,6 +290,17 @@ class Optimizer:
         c = self.cfg
         return [c.lr, c.beta1, c.beta2, c.resolved_eps(), c.momentum, c.rho]
 
+    @property
+    def global_norm(self):
+        """The last step's global gradient norm (after gscale, before clipping) as a 1-element device
+        tensor - read it on the host (``.item()``) only when it is wanted; None without clip_norm."""
+        return None if self.clip is None else self.clip.out[:1]
+
+    @property
+    def clip_out(self):
+        """[norm, scale] of the last step's clip (2-float device tensor); None without clip_norm."""
+        return None if self.clip is None else self.clip.out
+
     def step(self, grad=None, grad16=None, gscale: float = 1.0, gs_inc: int = 1, wait=None):
         """Apply gradients (default: the FlatParams grad buffer) to var_list.  ``wait`` (GPU; ignored
         on the CPU) = ``(done, seen, var_names)``: the launch's items of those variables wait on the
@@ -251,13 +308,17 @@ class Optimizer:
         gradient's producer on another stream); the launch then advances ``seen``."""
         if grad is None and grad16 is None:
             grad = self.P.grad
+        if self.clip_norm > 0 and wait is not None:
+            # the norm needs every gradient of the var list before the first update
+            raise ValueError("Optimizer.step: clip_norm cannot be combined with wait= (a gradient still in flight)")
         wait = (None, None, 0) if wait is None else (wait[0], wait[1], self._wait_mask(wait[2]))
+        clip = self.clip.compute(grad, grad16, gscale) if self.clip is not None else None
         if self.device.type == "cuda":
             ops.apply_gradients(self.kind, self.P.master, grad, grad16, gscale, self.s1, self.s2, *self._hyper(),
                                 self.beta_pow, self.global_step, gs_inc, self.done, self._blob, self.nseg,
-                                self.nwork, *wait)
+                                self.nwork, *wait, clip_scale=clip)
             return
-        self._step_cpu(grad if grad is not None else grad16.float(), gscale, gs_inc)
+        self._step_cpu(grad if grad is not None else grad16.float(), gscale, gs_inc, clip)
 
     @staticmethod
     def step_all(opts, gs_incs, grad=None, grad16=None, gscale: float = 1.0):
@@ -269,18 +330,23 @@ class Optimizer:
         if len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and all(o.device.type == "cuda" for o in opts):
             P = opts[0].P
             assert all(o.P is P for o in opts)
+            # one norm launch per clipping optimizer, then the one grouped apply reads each one's scale
+            clips = [o.clip.compute(grad, grad16, gscale) if o.clip is not None else None for o in opts]
             ops.require().apply_gradients_group(
                 kinds.pop(), P.master, P.grad if grad is None and grad16 is None else grad, grad16, gscale,
                 [o.s1 for o in opts], [o.s2 for o in opts], [h for o in opts for h in o._hyper()],
                 [o.beta_pow for o in opts], [o.global_step for o in opts], list(gs_incs), [o.done for o in opts],
-                [o._blob for o in opts], [o.nseg for o in opts], [o.nwork for o in opts])
+                [o._blob for o in opts], [o.nseg for o in opts], [o.nwork for o in opts],
+                clips if any(c is not None for c in clips) else None)
             return
         for o, inc in zip(opts, gs_incs):
             o.step(grad=grad, grad16=grad16, gscale=gscale, gs_inc=inc)
 
     @torch.no_grad()
-    def _step_cpu(self, grad, gscale, gs_inc):
+    def _step_cpu(self, grad, gscale, gs_inc, clip=None):
         c = self.cfg
+        if clip is not None:  # g * (gscale * scale), as the kernel forms it
+            gscale = float(gscale) * float(clip[0])
         lr_t = c.lr
         if c.kind == "adam":
             b1p, b2p = self.beta_pow.tolist()

@@ -36,7 +36,7 @@ from .models.mnist_cnn import MnistCnnModel
 from .models.resnet import ResNetModel
 from .models.softmax_reg import SoftmaxRegressionModel
 from .models.autoencoder import LR as ENC_LR
-from .optim import Optimizer
+from .optim import GlobalNormClip, Optimizer
 from .parallel.allreduce import BucketAllReduce
 from .parallel.comm import make_comm
 from .parallel.cluster import ClusterSpec, Server
@@ -112,6 +112,19 @@ def model_step_hook(model, step, metrics, log):
     if model.name == "gan" and (step % 1000 == 0 or step == 1):
         log("Step %i: Generator Loss: %f, Discriminator Loss: %f"
             % (step, float(metrics["gen_loss"].item()), float(metrics["disc_loss"].item())))
+
+
+CNN_CLIP_ERROR = ("--clip_norm: the MNIST CNN's own schedule applies its fc and conv gradients in separate "
+                  "Adam launches and sends its buckets from inside backward, so it cannot form one global norm "
+                  "before its first update; pass --bucket_mb to run the CNN on the generic path, which clips")
+
+
+def clip_metrics(clips) -> dict:
+    """The step's global gradient norms, read from the device: ``global_norm`` for a single optimizer,
+    ``global_norm_<i>`` per optimizer of several (the GAN).  A host read: log steps only."""
+    if len(clips) == 1:
+        return {"global_norm": float(clips[0].norm.item())}
+    return {"global_norm_%d" % i: float(c.norm.item()) for i, c in enumerate(clips)}
 
 
 class MetricsLog:
@@ -284,6 +297,19 @@ def run_worker_ps(flags, model, server, device, log):
     placement, shard_specs = _shard_layout(model, len(cl.ps))
     gs_rank = cl.rank_of("ps", placement[model.gs_name])
     prog = full_model.program(device, flags.batch_size, seed=flags.seed)
+    # --clip_norm: the worker clips before it pushes, as TF does (the ps applies what it receives):
+    # one global norm per minimize call over its var list, then the gradient scaled in place
+    clips = []
+    if flags.clip_norm > 0:
+        if hasattr(getattr(prog, "core", None), "allreduce") and flags.bucket_mb is None:
+            raise ValueError(CNN_CLIP_ERROR)
+        clips = [GlobalNormClip(prog.P, vl, flags.clip_norm) for _cfg, vl, _bp in full_model.opt_groups]
+
+    def clip_grads():
+        for c in clips:
+            c.compute()
+            c.scale_grad()
+
     if isinstance(model, PartitionedModel):
         model.add_aliases(prog.P)  # the parts as views of the worker's full variables
     comm = "cpu" if server.backend == "gloo" else device
@@ -317,7 +343,9 @@ def run_worker_ps(flags, model, server, device, log):
         link = ps_native.NativePSLink(server, prog.P, placement, shard_specs, placement[model.gs_name], device,
                                       buckets=_ps_buckets(prog, flags.bucket_mb))
         core = getattr(prog, "core", None)
-        if core is not None and hasattr(core, "allreduce"):
+        if clips:
+            pass                        # clipping: every bucket is pushed after the scaling (end_step)
+        elif core is not None and hasattr(core, "allreduce"):
             core.allreduce = link       # the CNN program pushes its buckets from inside backward
         elif hasattr(prog, "grad_ready"):
             prog.grad_ready = link.ready
@@ -325,6 +353,7 @@ def run_worker_ps(flags, model, server, device, log):
 
     def native_step():
         state["m"] = prog.compute_grads()
+        clip_grads()
         link.end_step()    # push what backward has not pushed yet, request / wait / pull
 
     runner = StepGraph(native_step, warmup=2, capture_error_mode="thread_local",
@@ -349,14 +378,18 @@ def run_worker_ps(flags, model, server, device, log):
                     prog.check_health()
             else:
                 metrics = prog.compute_grads()
+                clip_grads()
                 step = client.push_pull(prog.P.grad)
             if flags.check_pull:
                 log("pull checksum gs=%d: %.9e" % (step, float(prog.P.master.double().sum().item())))
+                log("pull l2norm gs=%d: %.9e" % (step, float(prog.P.master.double().norm().item())))
             faults.step(step)
             elapsed = time.time() - t0
             ips = prog.batch_size / max(elapsed, 1e-9)
             sc = scalar_metrics(metrics)
             if local_step % flags.log_every == 0:
+                if clips:
+                    sc.update(clip_metrics(clips))
                 log(step_line(step, local_step, elapsed * 1000, flags.py2_print))
                 sv.summary(step, dict(sc, **{"images/sec": ips}))
             model_step_hook(model, step, metrics, log)
@@ -384,10 +417,18 @@ def run_worker_ps(flags, model, server, device, log):
 # --------------------------------------------------------------- allreduce
 def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=None):
     prog = model.program(device, flags.batch_size, seed=flags.seed)
+    # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
+    # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
+    # with --clip_norm, which that schedule cannot do)
+    native = (hasattr(prog, "attach_data_parallel") and len(model.opt_groups) == 1
+              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0)))
+    if native and flags.clip_norm > 0:
+        raise ValueError(CNN_CLIP_ERROR)
     gstep = torch.zeros(1, dtype=torch.int32, device=device)
     opts = []
     for i, (cfg, var_list_, bp) in enumerate(model.opt_groups):
         cfg.lr = flags.learning_rate if flags.learning_rate is not None else cfg.lr
+        cfg.clip_norm = flags.clip_norm
         opts.append(Optimizer(cfg, prog.P, var_list=var_list_, global_step=gstep, beta_power_names=bp))
     is_chief = rank == 0
     sv = Supervisor(
@@ -400,10 +441,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         max_to_keep=flags.max_to_keep, log=log)
     sv.prepare()
     ar = None
-    # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
-    # here too, unless --bucket_mb asks for generic flat-buffer buckets
-    native = (hasattr(prog, "attach_data_parallel") and len(opts) == 1
-              and (world == 1 or flags.bucket_mb is None))
+    clips = [o.clip for o in opts if o.clip is not None]
     if world > 1:
         # chief's (possibly restored) state is the starting point of every replica
         dist.broadcast(prog.P.master, src=0, group=group)
@@ -485,6 +523,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
             elapsed = time.time() - t0
             ips = prog.batch_size * world / max(elapsed, 1e-9)
             sc = scalar_metrics(state.get("m"))
+            if clips and local_step % flags.log_every == 0:
+                sc.update(clip_metrics(clips))  # (the all-reduce has completed before step_all: every rank's norm)
             if local_step == 0 and native and ar is not None and is_chief:
                 log("schedule: " + " < ".join(prog.core.schedule))
             if local_step % flags.log_every == 0:

@@ -96,6 +96,11 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                     help="--mode=ps: split every variable larger than this many MB (fp32) into partitions "
                          "'<var>/part_<i>' dealt round-robin over the ps tasks (tf.variable_axis_size_partitioner "
                          "semantics; checkpoints keep the TF slice layout).  0: whole variables, as the reference")
+    ap.add_argument("--clip_norm", type=float, default=0.0,
+                    help="clip each optimizer's gradients by their global norm (tf.clip_by_global_norm over the "
+                         "minimize call's var list, after the 1/world averaging) on the device, inside the "
+                         "captured step; 0 (default): off, the reference's behaviour.  ps mode: the worker clips "
+                         "before it pushes.  The MNIST CNN's own schedule cannot clip: add --bucket_mb")
     ap.add_argument("--metrics_jsonl", default="", help="append {step, gs, ms, images/sec, loss} lines here")
     ap.add_argument("--heartbeat_secs", type=float, default=None,
                     help="publish a TCPStore heartbeat every N s; 0: off.  Default: %s s in --mode=allreduce "
@@ -105,7 +110,7 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                     help="ps: count a worker silent for this long as lost; all-reduce: a rank whose peer "
                          "is silent this long aborts the collectives and exits non-zero (with --heartbeat_secs)")
     add_bool(ap, "phase_timers", False, "time fwd+bwd / comm / apply per step with hipEvents (no hipGraph)")
-    add_bool(ap, "check_pull", False, "debug: checksum the pulled parameters every step (ps mode) / the "
+    add_bool(ap, "check_pull", False, "debug: checksum (and L2 norm of) the pulled parameters every step (ps mode) / the "
                                       "replicas' parameters at the end (all-reduce mode)")
     ap.add_argument("--trace_json", default="", help="write the per-step phase timings as a Chrome trace "
                                                      "(chrome://tracing / Perfetto); implies --phase_timers")
@@ -117,4 +122,6 @@ def parse(argv=None, model_defaults=None, prog=None):
     args, unknown = ap.parse_known_args(argv)
     if unknown:
         ap.error("unknown flags: %s" % " ".join(unknown))
+    if not args.clip_norm >= 0:
+        ap.error("--clip_norm must be >= 0 (0 = off), got %r" % args.clip_norm)
     return args
