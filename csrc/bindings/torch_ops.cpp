@@ -7,8 +7,10 @@
 #include <ATen/hip/HIPContext.h>
 #include <torch/custom_class.h>
 #include <torch/library.h>
+#include <algorithm>
 #include <vector>
 
+#include "../kernels/augment.h"
 #include "../kernels/conv.h"
 #include "../kernels/conv_f32.h"
 #include "../kernels/imgconv.h"
@@ -844,6 +846,83 @@ void gather_rows(const Tensor& src, const Tensor& dst, const optional<Tensor>& i
   dtfe::launch_gather_rows(a, cur_stream());
 }
 
+// gather_rows for image rows with the input transforms in the same launch (kernels/augment.h)
+void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, int64_t C, int64_t pad, bool flip,
+                  const optional<Tensor>& mean, const optional<Tensor>& inv_std, const optional<Tensor>& idx,
+                  const optional<Tensor>& labels_src, const optional<Tensor>& labels_dst, int64_t seed,
+                  const optional<Tensor>& counter, const optional<Tensor>& done, at::TensorList zero,
+                  const optional<Tensor>& onehot) {
+  auto i32 = [](const optional<Tensor>& t, const char* name, int64_t min_numel) {
+    if (!t.has_value() || !t->defined()) return;
+    check_cuda(*t, name);
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() >= min_numel, "augment_rows: ", name,
+                " must be contiguous int32 with at least ", min_numel, " elements");
+  };
+  auto given = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  check_cuda(src, "src");
+  check_cuda(dst, "dst");
+  TORCH_CHECK(src.get_device() == dst.get_device(), "augment_rows: src and dst on one device");
+  TORCH_CHECK(src.is_contiguous() && dst.is_contiguous(), "augment_rows: src and dst must be contiguous");
+  TORCH_CHECK(src.scalar_type() == at::kByte || src.scalar_type() == at::kFloat, "augment_rows: src must be uint8 or f32");
+  TORCH_CHECK(dst.scalar_type() == at::kFloat || dst.scalar_type() == at::kBFloat16,
+              "augment_rows: dst must be f32 or bf16");
+  TORCH_CHECK(H >= 1 && W >= 1 && C >= 1 && H * W * C < (int64_t(1) << 31), "augment_rows: bad image shape");
+  const int64_t D = H * W * C;
+  TORCH_CHECK(src.dim() == 2 && src.size(0) >= 1 && src.size(0) < (int64_t(1) << 31) && src.size(1) == D,
+              "augment_rows: src must be [n_rows][H*W*C]");
+  TORCH_CHECK(dst.dim() >= 1 && dst.size(0) >= 1 && dst.size(0) < (int64_t(1) << 31) && dst.numel() == dst.size(0) * D,
+              "augment_rows: dst must hold [B][H][W][C]");
+  TORCH_CHECK(pad >= 0 && pad <= dtfe::AUG_MAX_PAD && pad < std::min(H, W),
+              "augment_rows: 0 <= pad <= 15 and pad < min(H, W)");
+  TORCH_CHECK(given(mean) == given(inv_std), "augment_rows: mean and inv_std come together");
+  dtfe::AugmentArgs a{};
+  if (given(mean)) {
+    for (const Tensor* t : {&*mean, &*inv_std}) {
+      check_cuda(*t, "statistics");
+      TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == C,
+                  "augment_rows: mean / inv_std must be contiguous f32 [C]");
+    }
+    a.mean = mean->data_ptr<float>();
+    a.inv_std = inv_std->data_ptr<float>();
+  }
+  const int64_t B = dst.size(0);
+  i32(idx, "idx", B);
+  i32(labels_src, "labels_src", src.size(0));
+  i32(labels_dst, "labels_dst", B);
+  TORCH_CHECK(!given(labels_dst) || given(labels_src), "augment_rows: labels_dst needs labels_src");
+  if (given(onehot)) {
+    check_cuda(*onehot, "onehot");
+    TORCH_CHECK(onehot->scalar_type() == at::kFloat && onehot->is_contiguous() && onehot->dim() == 2 &&
+                    onehot->size(0) == B && given(labels_src),
+                "augment_rows: onehot must be contiguous f32 [B][ncls] and needs labels_src");
+    a.onehot = onehot->data_ptr<float>();
+    a.ncls = (int)onehot->size(1);
+  }
+  if (given(counter)) {
+    check_cuda(*counter, "counter");
+    TORCH_CHECK(counter->scalar_type() == at::kLong && counter->numel() >= 1, "augment_rows: counter must be int64");
+  }
+  if (given(done)) {
+    check_cuda(*done, "done");
+    TORCH_CHECK(done->element_size() == 4 && done->numel() >= 1, "augment_rows: done must be one 32-bit word");
+  }
+  TORCH_CHECK(zero.size() <= 4, "augment_rows: at most 4 zero ranges");
+  for (const Tensor& z : zero) {
+    check_cuda(z, "zero");
+    TORCH_CHECK(z.is_contiguous() && (z.numel() * z.element_size()) % 4 == 0, "augment_rows: zero ranges must be "
+                "contiguous whole 32-bit words");
+    a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
+    a.zlen[a.nz++] = (long)(z.numel() * z.element_size() / 4);
+  }
+  a.src = src.data_ptr(); a.src_dtype = data_code(src); a.n_rows = src.size(0);
+  a.dst = dst.data_ptr(); a.dst_dtype = data_code(dst); a.B = (int)B;
+  a.H = (int)H; a.W = (int)W; a.C = (int)C; a.pad = (int)pad; a.flip = flip ? 1 : 0;
+  a.idx = ptr_or_null<int32_t>(idx);
+  a.labels_src = ptr_or_null<int32_t>(labels_src); a.labels_dst = ptr_or_null<int32_t>(labels_dst);
+  a.seed = (uint64_t)seed; a.counter = ptr_or_null<int64_t>(counter); a.done = ptr_or_null<uint32_t>(done);
+  dtfe::launch_augment_rows(a, cur_stream());
+}
+
 void uniform_fill(const Tensor& out, double lo, double hi, int64_t seed, const optional<Tensor>& counter,
                   const optional<Tensor>& done, const optional<Tensor>& copy_src, const optional<Tensor>& copy_dst) {
   check_cuda(out, "out");
@@ -1395,6 +1474,10 @@ TORCH_LIBRARY(dtfe, m) {
   m.def(
       "gather_rows(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? labels_src, Tensor(b!)? labels_dst, int seed,"
       " Tensor(c!)? counter, Tensor(d!)? done, Tensor(e!)[] zero, Tensor(f!)? onehot=None) -> ()");
+  m.def(
+      "augment_rows(Tensor src, Tensor(a!) dst, int H, int W, int C, int pad, bool flip, Tensor? mean, Tensor? inv_std,"
+      " Tensor? idx, Tensor? labels_src, Tensor(b!)? labels_dst, int seed, Tensor(c!)? counter, Tensor(d!)? done,"
+      " Tensor(e!)[] zero, Tensor(f!)? onehot=None) -> ()");
   m.def("uniform_fill(Tensor(a!) out, float lo, float hi, int seed, Tensor(b!)? counter, Tensor(c!)? done,"
         " Tensor? copy_src=None, Tensor(d!)? copy_dst=None) -> ()");
   m.def("cast_(Tensor src, Tensor(a!) dst) -> ()");
@@ -1448,6 +1531,7 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("scale_", &scale_);
   m.impl("gather_rows", &gather_rows);
+  m.impl("augment_rows", &augment_rows);
   m.impl("seq_stage", &seq_stage);
   m.impl("wgrad_tallk", &wgrad_tallk);
   m.impl("uniform_fill", &uniform_fill);

@@ -10,15 +10,63 @@ deterministic synthetic CIFAR-shaped set is generated and that is logged.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 
 import numpy as np
+import torch
 
 from .mnist import DataSet, DataSets
 
 IMG, CH, NCLS = 32, 3, 10
 TRAIN_FILES = ["data_batch_%d.bin" % i for i in range(1, 6)]
 TEST_FILE = "test_batch.bin"
+
+
+def channel_stats(images_u8):
+    """(mean, inv_std) per channel of pixels / 255 over the whole array (any shape whose last axis
+    splits into CH channels), returned as float32 [CH].  Exact integer sums of the bytes and their
+    squares (in blocks: no float64 copy of the training set), then float64: the population
+    standard deviation, as numpy's."""
+    px = np.asarray(images_u8).reshape(-1, CH)
+    s, q = np.zeros(CH, dtype=np.int64), np.zeros(CH, dtype=np.int64)
+    for lo in range(0, px.shape[0], 1 << 20):
+        blk = px[lo:lo + (1 << 20)].astype(np.int64)
+        s += blk.sum(0)
+        q += (blk * blk).sum(0)
+    mean = s / (px.shape[0] * 255.0)
+    var = q / (px.shape[0] * 255.0 * 255.0) - mean * mean
+    if not (var > 0).all():
+        raise ValueError("channel_stats: a channel is constant, it cannot be standardised")
+    return mean.astype(np.float32), (1.0 / np.sqrt(var)).astype(np.float32)
+
+
+@dataclasses.dataclass(frozen=True)
+class Augment:
+    """The input transforms ``ops.augment_rows`` applies to a batch: crop of the ``pad``-padded image,
+    horizontal flip, per-channel standardisation (``mean`` / ``inv_std``: float32 numpy [C])."""
+    H: int
+    W: int
+    C: int
+    pad: int
+    flip: bool
+    mean: np.ndarray
+    inv_std: np.ndarray
+
+    @classmethod
+    def cifar(cls, train_images_u8):
+        """The usual CIFAR-10 recipe: 4-pixel pad + random 32x32 crop, random flip, training-set statistics."""
+        mean, inv_std = channel_stats(train_images_u8)
+        return cls(IMG, IMG, CH, 4, True, mean, inv_std)
+
+    def eval(self):
+        """The evaluation-time transform: the same statistics, no crop, no flip."""
+        return dataclasses.replace(self, pad=0, flip=False)
+
+    def stats_on(self, device):
+        """(mean, inv_std) as float32 tensors on ``device``."""
+        return (torch.from_numpy(np.ascontiguousarray(self.mean)).to(device),
+                torch.from_numpy(np.ascontiguousarray(self.inv_std)).to(device))
 
 
 def _read_bin(path):

@@ -48,6 +48,7 @@ class DataSet:
         self.labels_int = labels.astype(np.int64)
         self.one_hot = one_hot
         self.num_classes = num_classes
+        self.seed = seed
         self._batcher = native.rt().EpochBatcher(self.num_examples, seed)
 
     @property
@@ -130,10 +131,21 @@ def read_data_sets(data_dir: str, one_hot: bool = True, validation_size: int = 5
 
 
 class DeviceBatcher:
-    """HBM-resident copy of a DataSet; batches gathered on device (K14)."""
+    """HBM-resident copy of a DataSet; batches gathered on device (K14).
 
-    def __init__(self, ds: DataSet, device, batch_size: int, one_hot: bool = True):
+    ``augment`` (a ``data.cifar.Augment``): every batch goes through ONE ``ops.augment_rows`` launch -
+    rows from the host epoch indices as without it, crop / flip draws from a device counter the
+    batcher owns (seeded with the DataSet's seed, starting at 0), standardised pixels and the labels
+    (one-hot rows included) written by that launch.  ``out``: its destination instead of ``self.x``,
+    e.g. the program's bf16 input buffer, which then needs no further copy."""
+
+    def __init__(self, ds: DataSet, device, batch_size: int, one_hot: bool = True, augment=None, out=None):
         from .. import ops
+
+        if out is not None and augment is None:
+            raise ValueError("DeviceBatcher: out= is the destination of the augmenting launch, it needs augment=")
+        self.augment = augment
+        self.out = out
 
         self.ops = ops
         self.ds = ds
@@ -148,10 +160,23 @@ class DeviceBatcher:
         self.one_hot = one_hot
         self._host_idx = torch.empty(batch_size, dtype=torch.int32).pin_memory() \
             if self.device.type == "cuda" else torch.empty(batch_size, dtype=torch.int32)
+        if augment is not None:
+            self.aug_stats = augment.stats_on(self.device)
+            self.aug_seed = ds.seed
+            self.aug_ctr = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.aug_done = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def next_batch(self):
         self._host_idx.copy_(torch.from_numpy(self.ds.next_batch_indices(self.B)))
         self.idx.copy_(self._host_idx, non_blocking=True)
+        if self.augment is not None:
+            a = self.augment
+            x = self.x if self.out is None else self.out
+            self.ops.augment_rows(self.images, x, a.H, a.W, a.C, pad=a.pad, flip=a.flip, mean=self.aug_stats[0],
+                                  inv_std=self.aug_stats[1], idx=self.idx, labels_src=self.labels,
+                                  labels_dst=self.y_int, seed=self.aug_seed, counter=self.aug_ctr, done=self.aug_done,
+                                  onehot=self.y if self.one_hot else None)
+            return x, (self.y if self.one_hot else self.y_int)
         self.ops.gather_rows(self.images, self.x, self.idx, self.labels, self.y_int)
         if self.one_hot:
             self.y.zero_()

@@ -727,6 +727,9 @@ class ResNetProgram(StepProgram):
         self.dense_lo = min(P.offsets[d.kernel], P.offsets[d.bias])
         self.grad_ready = None  # optional backward-progress hook (BucketAllReduce.ready)
         self.training = True    # False inside evaluate(): no fused head (it writes gradients), no BN folds
+        # (mean, inv_std) f32 [C] on the device when the training batches are standardised (--augment):
+        # evaluate() then standardises its images the same way, without crop or flip
+        self.input_norm = None
         self._defer_convs = [c for b in L["blocks"] for c in (b.conv1, b.conv2, getattr(b, "conv3", None))
                              if c is not None and c.img_wgrad and c.cin % 16 == 0 and B >= 128]
         self._defer_ok = self.device.type == "cuda" and _WGRAD_DEFER and 0 < len(self._defer_convs) <= 32
@@ -772,7 +775,8 @@ class ResNetProgram(StepProgram):
 
     def load_batch(self, batch):
         x, y = batch
-        self.x.copy_(x.reshape(self.x.shape).to(self.x.dtype))
+        if x is not self.x:  # (a batcher that writes straight into self.x hands it back: nothing to copy)
+            self.x.copy_(x.reshape(self.x.shape).to(self.x.dtype))
         yy = y.reshape(self.batch_size, -1)
         if yy.shape[1] == 1:
             self.y.zero_()
@@ -896,7 +900,13 @@ class ResNetProgram(StepProgram):
             for lo in range(0, n, B):
                 m = min(B, n - lo)
                 idx = torch.arange(lo, lo + B, device=images.device).clamp_max(n - 1)
-                self.load_batch((images[idx], labels[idx]))
+                if self.input_norm is not None:
+                    H, W, C = self.x.shape[1:]
+                    ops.augment_rows(images.reshape(n, -1).contiguous(), self.x, H, W, C, mean=self.input_norm[0],
+                                     inv_std=self.input_norm[1], idx=idx.int())
+                    self.load_batch((self.x, labels[idx]))
+                else:
+                    self.load_batch((images[idx], labels[idx]))
                 self.forward()
                 hits += int((self.logits[:m].argmax(1) == self.y[:m].argmax(1)).sum().item())
         finally:

@@ -29,6 +29,7 @@ __all__ = [
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
+    "augment_rows", "augment_draws", "AUG_SALT",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -155,6 +156,24 @@ def hash_u32(seed, idx):
 def hash_uniform(seed, idx):
     """Host mirror of common.h hash_uniform: the top 24 bits of hash_u32 -> fp32 uniform [0, 1)."""
     return (hash_u32(seed, idx) >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+AUG_SALT = 0xC1FA5A17D00D5EED  # csrc/kernels/augment.h: the crop / flip draws' stream is hash_u32(seed ^ AUG_SALT, .)
+AUG_MAX_PAD = 15
+
+
+def augment_draws(seed, step, B, pad, flip):
+    """Host mirror of augment_rows' per-sample draws at counter value ``step``: (dy, dx, flipped),
+    int64 / int64 / bool arrays [B].  h = hash_u32(seed ^ AUG_SALT, step * B + b), span = 2 * pad + 1:
+    dx = h % span, dy = (h / span) % span, flipped = flip and bit 0 of h / span^2."""
+    m64 = 0xFFFFFFFFFFFFFFFF
+    i = np.uint64((int(step) * int(B)) & m64) + np.arange(B, dtype=np.uint64)
+    h = hash_u32((int(seed) & m64) ^ AUG_SALT, i).astype(np.int64)
+    span = 2 * int(pad) + 1
+    dx = h % span
+    dy = (h // span) % span
+    flipped = ((h // (span * span)) & 1).astype(bool) & bool(flip)
+    return dy, dx, flipped
 
 
 def _dropout_ref(x, idx, keep, seed, base):
@@ -817,6 +836,76 @@ def gather_rows(src, dst, idx=None, labels_src=None, labels_dst=None, seed=0, co
     dst.copy_(rows.reshape(dst.shape).to(dst.dtype))
     if labels_dst is not None:
         labels_dst.copy_(labels_src[idx.long()])
+    return dst
+
+
+def _augment_check(src, dst, H, W, C, pad, mean, inv_std):
+    """The argument checks of torch.ops.dtfe.augment_rows, as ValueError on either device."""
+    H, W, C, pad = int(H), int(W), int(C), int(pad)
+    if src.dtype not in (torch.uint8, torch.float32) or dst.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("augment_rows: src must be uint8 or f32, dst f32 or bf16 (got %s -> %s)" % (src.dtype, dst.dtype))
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("augment_rows: src and dst must be contiguous")
+    if src.device != dst.device:
+        raise ValueError("augment_rows: src on %s, dst on %s" % (src.device, dst.device))
+    if min(H, W, C) < 1 or src.dim() != 2 or src.shape[0] < 1 or src.shape[1] != H * W * C:
+        raise ValueError("augment_rows: src %s is not [n_rows][H*W*C = %d]" % (tuple(src.shape), H * W * C))
+    if dst.dim() < 1 or dst.shape[0] < 1 or dst.numel() != dst.shape[0] * H * W * C:
+        raise ValueError("augment_rows: dst %s does not hold [B][%d][%d][%d]" % (tuple(dst.shape), H, W, C))
+    if not (0 <= pad <= AUG_MAX_PAD and pad < min(H, W)):
+        raise ValueError("augment_rows: pad %d: needs 0 <= pad <= %d and pad < min(H, W)" % (pad, AUG_MAX_PAD))
+    if (mean is None) != (inv_std is None):
+        raise ValueError("augment_rows: mean and inv_std come together")
+    for t in (mean, inv_std):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != C or not t.is_contiguous()
+                              or t.device != dst.device):
+            raise ValueError("augment_rows: mean / inv_std must be contiguous f32 [C = %d] on %s" % (C, dst.device))
+
+
+def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, idx=None, labels_src=None,
+                 labels_dst=None, seed=0, counter=None, done=None, zero=(), onehot=None):
+    """gather_rows for image rows [n_rows][H*W*C] (uint8 scaled by 1/255, or f32) -> dst [B][H][W][C]
+    (f32 / bf16) with the input transforms in the same launch.  Sample b at counter value s draws
+    (dy, dx, flipped) = augment_draws(seed, s, B, pad, flip)[b] and
+        dst[b, y, x, c] = img(y + dy - pad, (W - 1 - x if flipped else x) + dx - pad, c)
+    with img() = 0 outside the image (the border is zero AFTER standardisation: the mean colour) and
+    (v - mean[c]) * inv_std[c] in fp32 inside it (``mean`` None: v).  Rows, labels, one-hot rows, zero
+    ranges and the (seed, counter, done) ticket are gather_rows'; ``idx`` None samples the rows
+    hash_u32(seed, s * B + b) % n_rows.  pad = 0, flip off, no statistics: gather_rows bit for bit."""
+    _augment_check(src, dst, H, W, C, pad, mean, inv_std)
+    H, W, C, pad = int(H), int(W), int(C), int(pad)
+    if dst.is_cuda:
+        require().augment_rows(src, dst, H, W, C, pad, bool(flip), mean, inv_std, idx, labels_src, labels_dst, seed,
+                               counter, done, list(zero), onehot)
+        return dst
+    B = dst.shape[0]
+    s = int(counter.reshape(-1)[0].item()) if counter is not None else 0
+    if idx is not None:
+        rows = idx.reshape(-1)[:B].long()
+    else:
+        i = np.uint64((s * B) & 0xFFFFFFFFFFFFFFFF) + np.arange(B, dtype=np.uint64)
+        rows = torch.from_numpy((hash_u32(seed, i) % np.uint32(src.shape[0])).astype(np.int64))
+    dy, dx, fl = (torch.from_numpy(a) for a in augment_draws(seed, s, B, pad, flip))
+    img = src[rows].reshape(B, H, W, C)
+    if src.dtype == torch.uint8:  # the kernel's load: byte * (1.f / 255.f), one fp32 rounding
+        img = img.float() * torch.tensor(float(np.float32(1.0) / np.float32(255.0)))
+    if mean is not None:
+        img = (img - mean.reshape(1, 1, 1, C)) * inv_std.reshape(1, 1, 1, C)
+    ys = torch.arange(H).reshape(1, H) + (dy.reshape(B, 1) - pad)
+    x = torch.arange(W).reshape(1, W)
+    xs = torch.where(fl.reshape(B, 1), W - 1 - x, x) + (dx.reshape(B, 1) - pad)
+    inside = ((ys >= 0) & (ys < H)).reshape(B, H, 1, 1) & ((xs >= 0) & (xs < W)).reshape(B, 1, W, 1)
+    got = img[torch.arange(B).reshape(B, 1, 1), ys.clamp(0, H - 1).reshape(B, H, 1), xs.clamp(0, W - 1).reshape(B, 1, W)]
+    dst.copy_(torch.where(inside, got, torch.zeros((), dtype=got.dtype)).reshape(dst.shape).to(dst.dtype))
+    if labels_dst is not None:
+        labels_dst.copy_(labels_src[rows])
+    if onehot is not None:
+        onehot.zero_()
+        onehot.scatter_(1, labels_src[rows].long().unsqueeze(1), 1.0)
+    for z in zero:
+        z.zero_()
+    if counter is not None and done is not None:  # the kernel's ticket needs both
+        counter += 1
     return dst
 
 

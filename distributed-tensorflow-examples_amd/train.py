@@ -25,7 +25,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ckpt
+from . import ckpt, ops
 from .data import cifar, imagenet_synth
 from .data.mnist import DeviceBatcher, read_data_sets as read_mnist
 from .models.autoencoder import AutoencoderModel
@@ -138,19 +138,50 @@ class MetricsLog:
 
 
 # ---------------------------------------------------------------- batching
-class Feeder:
-    """next batch for a program: host next_batch on CPU, HBM gather on GPU."""
+def check_augment(augment: str, model):
+    """--augment cifar is the CIFAR-10 recipe: only the CIFAR model (resnet20) takes it."""
+    if augment != "none" and getattr(model, "name", "") != "resnet20":
+        raise ValueError("--augment %s: the CIFAR-10 input transforms (32x32x3 crop / flip / channel statistics) "
+                         "apply to --model resnet20 only, not to %r" % (augment, getattr(model, "name", "")))
 
-    def __init__(self, data, program, device):
+
+class Feeder:
+    """next batch for a program: host next_batch on CPU, HBM gather on GPU.
+
+    ``augment`` ("none" / "cifar", the --augment flag): the CIFAR input transforms on every training
+    batch - on GPUs inside the batcher's one launch, written straight into the program's input buffer;
+    on CPU ``ops.augment_rows`` over the host batch.  The draws are seeded with the training set's
+    seed (the per-rank data seed), and ``program.input_norm`` is set so that evaluation standardises too."""
+
+    def __init__(self, data, program, device, augment="none"):
         self.B = program.batch_size
         self.dev = None
+        self.aug = None
+        if augment != "none":
+            check_augment(augment, program.model)
+            self.aug = cifar.Augment.cifar(data.train.images_u8)
+            self.stats = program.input_norm = self.aug.stats_on(device)
         if device.type == "cuda":
-            self.dev = DeviceBatcher(data.train, device, self.B, one_hot=True)
+            self.dev = DeviceBatcher(data.train, device, self.B, one_hot=True, augment=self.aug,
+                                     out=program.x if self.aug is not None else None)
+        elif self.aug is not None:
+            self.x = torch.empty(self.B, self.aug.H * self.aug.W * self.aug.C)
+            self.ctr = torch.zeros(1, dtype=torch.int64)
+            self.done = torch.zeros(1, dtype=torch.int32)
         self.data = data
 
     def next(self):
         if self.dev is not None:
             return self.dev.next_batch()
+        if self.aug is not None:
+            a, train = self.aug, self.data.train
+            idx = torch.from_numpy(train.next_batch_indices(self.B).astype(np.int32))
+            ops.augment_rows(torch.from_numpy(train.images_u8), self.x, a.H, a.W, a.C, pad=a.pad, flip=a.flip,
+                             mean=self.stats[0], inv_std=self.stats[1], idx=idx, seed=train.seed, counter=self.ctr,
+                             done=self.done)
+            y = torch.zeros(self.B, train.num_classes)
+            y[torch.arange(self.B), torch.from_numpy(train.labels_int[idx.numpy()])] = 1.0
+            return self.x, y
         x, y = self.data.train.next_batch(self.B)
         return torch.from_numpy(x), torch.from_numpy(y)
 
@@ -327,7 +358,7 @@ def run_worker_ps(flags, model, server, device, log):
         max_to_keep=flags.max_to_keep, log=log)
     data = read_data_sets(model, "" if flags.synthetic else flags.data_dir, one_hot=True,
                           seed=flags.seed * 1000 + server.task_index + 1, log=log)
-    feeder = Feeder(data, prog, device)
+    feeder = Feeder(data, prog, device, augment=flags.augment)
     metrics_log = MetricsLog(flags.metrics_jsonl)
     hb = Heartbeat(server.store, "worker", server.task_index, flags.heartbeat_secs)
     faults = FaultInjector("worker", server.task_index, log=log)
@@ -469,7 +500,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         prog.attach_data_parallel(ar, opts[0])
     data = read_data_sets(model, "" if flags.synthetic else flags.data_dir, one_hot=True, seed=flags.seed * 1000 + rank + 1,
                           log=log if is_chief else (lambda *_: None))
-    feeder = Feeder(data, prog, device)
+    feeder = Feeder(data, prog, device, augment=flags.augment)
     metrics_log = MetricsLog(flags.metrics_jsonl)
 
     state = {}
@@ -621,6 +652,7 @@ def run(model_name: str, argv=None, log=_print):
         model.set_dtype(flags.dtype)  # --dtype: the model's program must implement it (no silent fallback)
     except ValueError as e:
         raise SystemExit(str(e))
+    check_augment(flags.augment, model)
     torch.manual_seed(flags.seed)
     np.random.seed(flags.seed)
     mode = flagmod.resolve_mode(flags)  # (+ mode-dependent defaults: --heartbeat_secs)

@@ -101,6 +101,12 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "minimize call's var list, after the 1/world averaging) on the device, inside the "
                          "captured step; 0 (default): off, the reference's behaviour.  ps mode: the worker clips "
                          "before it pushes.  The MNIST CNN's own schedule cannot clip: add --bucket_mb")
+    ap.add_argument("--augment", choices=["none", "cifar"], default="none",
+                    help="input transforms on the training batches: cifar = per-channel standardisation with the "
+                         "training set's statistics, 4-pixel zero pad + random 32x32 crop, random horizontal flip, "
+                         "in the batch-gather launch on GPUs (resnet20 only; its evaluation standardises too); "
+                         "none (default): pixels / 255 as they are.  The crop / flip draws are a counter-based "
+                         "stream seeded with the worker's data seed; a restart begins its counter at 0 again")
     ap.add_argument("--metrics_jsonl", default="", help="append {step, gs, ms, images/sec, loss} lines here")
     ap.add_argument("--heartbeat_secs", type=float, default=None,
                     help="publish a TCPStore heartbeat every N s; 0: off.  Default: %s s in --mode=allreduce "
