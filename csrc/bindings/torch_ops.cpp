@@ -581,8 +581,9 @@ void head_wgrad(const Tensor& dl, const Tensor& h, const Tensor& dw, const optio
 // -------------------------------------------------------------- optimizer
 // segs: int64 [nseg, 6] = (off, R, T, C, w16_ptr, wt16_ptr)
 // work: int64 [nwork, 7] = (kind, seg, t, r0, c0, start, count)
+// wd:   optional float32 [nseg], the L2 weight decay of each segment (absent: 0 everywhere)
 // returns a device blob holding both struct arrays
-Tensor opt_pack(const Tensor& segs, const Tensor& work, const Tensor& device_like) {
+Tensor opt_pack(const Tensor& segs, const Tensor& work, const Tensor& device_like, const optional<Tensor>& wd) {
   TORCH_CHECK(segs.device().is_cpu() && work.device().is_cpu(), "opt_pack: CPU int64 tables");
   auto S = segs.contiguous(), Wk = work.contiguous();
   const int64_t ns = S.size(0), nw = Wk.size(0);
@@ -590,9 +591,16 @@ Tensor opt_pack(const Tensor& segs, const Tensor& work, const Tensor& device_lik
   std::vector<dtfe::OptWork> vw(nw);
   const int64_t* s = S.data_ptr<int64_t>();
   const int64_t* w = Wk.data_ptr<int64_t>();
+  Tensor D;
+  if (wd.has_value() && wd->defined()) {
+    TORCH_CHECK(wd->device().is_cpu() && wd->scalar_type() == at::kFloat && wd->dim() == 1 && wd->size(0) == ns,
+                "opt_pack: wd is a CPU float32 [nseg] vector");
+    D = wd->contiguous();
+  }
   for (int64_t i = 0; i < ns; ++i) {
     vs[i].off = s[i * 6 + 0];
     vs[i].R = (int)s[i * 6 + 1]; vs[i].T = (int)s[i * 6 + 2]; vs[i].C = (int)s[i * 6 + 3];
+    vs[i].wd = D.defined() ? D.data_ptr<float>()[i] : 0.f;
     vs[i].w16 = reinterpret_cast<dtfe::bf16*>(s[i * 6 + 4]);
     vs[i].wt16 = reinterpret_cast<dtfe::bf16*>(s[i * 6 + 5]);
   }
@@ -699,6 +707,56 @@ void scale_(const Tensor& t, const Tensor& scale, const Tensor& plan) {
                             reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()), (int)plan.size(0), cur_stream());
 }
 
+// the device copy of an LrSchedule (optim.h).  kind: 0 constant, 1 piecewise, 2 linear.  The floats arrive
+// as the float32 values the host mirror (ops.lr_schedule_value) computes with, so the casts are exact
+Tensor lr_schedule_pack(int64_t kind, at::IntArrayRef bounds, at::ArrayRef<double> values, double lr, double end,
+                        int64_t decay_steps, double inv_decay, int64_t warmup, double inv_warmup,
+                        const Tensor& device_like) {
+  TORCH_CHECK(kind >= dtfe::LR_CONSTANT && kind <= dtfe::LR_LINEAR, "lr_schedule_pack: kind is 0, 1 or 2");
+  dtfe::LrSchedule h{};
+  h.kind = (int)kind;
+  if (kind == dtfe::LR_PIECEWISE) {
+    TORCH_CHECK(bounds.size() >= 1 && bounds.size() <= (size_t)dtfe::LR_MAX_BOUNDS && values.size() == bounds.size() + 1,
+                "lr_schedule_pack: 1..8 boundaries and one more value than boundaries");
+    h.nb = (int)bounds.size();
+    for (size_t i = 0; i < bounds.size(); ++i) {
+      TORCH_CHECK(bounds[i] >= 0 && bounds[i] <= INT32_MAX && (i == 0 || bounds[i] > bounds[i - 1]),
+                  "lr_schedule_pack: boundaries are strictly increasing int32 steps");
+      h.bounds[i] = (int)bounds[i];
+    }
+    for (size_t i = 0; i < values.size(); ++i) h.values[i] = (float)values[i];
+  }
+  if (kind == dtfe::LR_LINEAR)
+    TORCH_CHECK(decay_steps >= 1 && decay_steps <= INT32_MAX, "lr_schedule_pack: decay_steps >= 1");
+  TORCH_CHECK(warmup >= 0 && warmup <= INT32_MAX, "lr_schedule_pack: warmup >= 0");
+  h.lr = (float)lr; h.end = (float)end;
+  h.decay_steps = (int)decay_steps; h.inv_decay = (float)inv_decay;
+  h.warmup = (int)warmup; h.inv_warmup = (float)inv_warmup;
+  Tensor host = at::empty({(int64_t)sizeof(h)}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr(), &h, sizeof(h));
+  return host.to(device_like.device());
+}
+
+// the trailing optional arguments of both apply ops: schedule blob, rate output, flags
+void opt_extras(dtfe::OptArgs& a, const optional<Tensor>& sched, const optional<Tensor>& lr_out, bool nesterov, bool decay) {
+  if (sched.has_value() && sched->defined()) {
+    check_cuda(*sched, "sched");
+    TORCH_CHECK(sched->scalar_type() == at::kByte && sched->is_contiguous() &&
+                    sched->numel() == (int64_t)sizeof(dtfe::LrSchedule),
+                "apply_gradients: sched is the blob of lr_schedule_pack");
+    TORCH_CHECK(a.global_step, "apply_gradients: a learning-rate schedule needs a global_step");
+    a.sched = reinterpret_cast<const dtfe::LrSchedule*>(sched->data_ptr());
+  }
+  if (lr_out.has_value() && lr_out->defined()) {
+    check_cuda(*lr_out, "lr_out");
+    TORCH_CHECK(lr_out->scalar_type() == at::kFloat && lr_out->numel() >= 1, "apply_gradients: lr_out is a float32 scalar");
+    a.lr_out = lr_out->data_ptr<float>();
+  }
+  TORCH_CHECK(!nesterov || a.kind == dtfe::OPT_MOMENTUM, "apply_gradients: nesterov is for the momentum optimizer");
+  a.nesterov = nesterov ? 1 : 0;
+  a.decay = decay ? 1 : 0;
+}
+
 // wait_done / wait_seen / wait_segs: this launch's items of the segments in the bit mask wait on the
 // device-side counter pair (OptArgs::wait_done / wait_seen) - a gradient produced on another stream with
 // no graph edge to the optimizer launch (the CNN's conv2 weight-gradient branch)
@@ -707,7 +765,8 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
                      double beta2, double eps, double momentum, double rho, const optional<Tensor>& beta_pow,
                      const optional<Tensor>& global_step, int64_t gs_inc, const Tensor& done, const Tensor& blob,
                      int64_t nseg, int64_t nwork, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
-                     int64_t wait_segs, const optional<Tensor>& clip_scale) {
+                     int64_t wait_segs, const optional<Tensor>& clip_scale, const optional<Tensor>& sched,
+                     const optional<Tensor>& lr_out, bool nesterov, bool decay) {
   const double hyper[6] = {lr, beta1, beta2, eps, momentum, rho};
   dtfe::OptArgs a = opt_args(kind, p, g, g16, gscale, s1, s2, hyper, beta_pow, global_step, gs_inc, done, blob, nseg,
                              nwork);
@@ -724,6 +783,7 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
     a.wait_segs = (uint32_t)wait_segs;
   }
   a.clip_scale = clip_scale_ptr(clip_scale);
+  opt_extras(a, sched, lr_out, nesterov, decay);
   dtfe::launch_apply_gradients(a, cur_stream());
 }
 
@@ -735,18 +795,26 @@ void apply_gradients_group(int64_t kind, const Tensor& p, const optional<Tensor>
                            const c10::List<optional<Tensor>>& beta_pow,
                            const c10::List<optional<Tensor>>& global_step, at::IntArrayRef gs_inc,
                            at::TensorList done, at::TensorList blob, at::IntArrayRef nseg, at::IntArrayRef nwork,
-                           const optional<c10::List<optional<Tensor>>>& clip_scale) {
+                           const optional<c10::List<optional<Tensor>>>& clip_scale,
+                           const optional<c10::List<optional<Tensor>>>& sched,
+                           const optional<c10::List<optional<Tensor>>>& lr_out, at::OptionalIntArrayRef nesterov,
+                           at::OptionalIntArrayRef decay) {
   const size_t n = done.size();
   TORCH_CHECK(n >= 1 && n <= (size_t)dtfe::OPT_GROUP_MAX, "apply_gradients_group: 1..4 optimizers");
   TORCH_CHECK(s1.size() == n && s2.size() == n && hyper.size() == 6 * n && beta_pow.size() == n &&
                   global_step.size() == n && gs_inc.size() == n && blob.size() == n && nseg.size() == n &&
-                  nwork.size() == n && (!clip_scale.has_value() || clip_scale->size() == n),
+                  nwork.size() == n && (!clip_scale.has_value() || clip_scale->size() == n) &&
+                  (!sched.has_value() || sched->size() == n) && (!lr_out.has_value() || lr_out->size() == n) &&
+                  (!nesterov.has_value() || nesterov->size() == n) && (!decay.has_value() || decay->size() == n),
               "apply_gradients_group: one entry per optimizer in every list");
   dtfe::OptArgs q[dtfe::OPT_GROUP_MAX];
   for (size_t i = 0; i < n; ++i) {
     q[i] = opt_args(kind, p, g, g16, gscale, s1.get(i), s2.get(i), hyper.data() + 6 * i, beta_pow.get(i),
                     global_step.get(i), gs_inc[i], done[i], blob[i], nseg[i], nwork[i]);
     if (clip_scale.has_value()) q[i].clip_scale = clip_scale_ptr(clip_scale->get(i));
+    opt_extras(q[i], sched.has_value() ? sched->get(i) : optional<Tensor>(),
+               lr_out.has_value() ? lr_out->get(i) : optional<Tensor>(), nesterov.has_value() && (*nesterov)[i] != 0,
+               decay.has_value() && (*decay)[i] != 0);
   }
   dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
 }
@@ -1455,16 +1523,21 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("head_wgrad(Tensor dl, Tensor h, Tensor(a!) dw, Tensor(b!)? db, int nc, float scale, Tensor? parts=None,"
         " Tensor(c!)? loss_sum=None, Tensor(d!)? correct=None,"
         " __torch__.torch.classes.dtfe.GemmGroup? group=None) -> ()");
-  m.def("opt_pack(Tensor segs, Tensor work, Tensor device_like) -> Tensor");
+  m.def("opt_pack(Tensor segs, Tensor work, Tensor device_like, Tensor? wd=None) -> Tensor");
+  m.def(
+      "lr_schedule_pack(int kind, int[] bounds, float[] values, float lr, float end, int decay_steps, float inv_decay,"
+      " int warmup, float inv_warmup, Tensor device_like) -> Tensor");
   m.def(
       "apply_gradients(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor(b!)? s1, Tensor(c!)? s2,"
       " float lr, float beta1, float beta2, float eps, float momentum, float rho, Tensor(d!)? beta_pow,"
       " Tensor(e!)? global_step, int gs_inc, Tensor(f!) done, Tensor blob, int nseg, int nwork,"
-      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0, Tensor? clip_scale=None) -> ()");
+      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0, Tensor? clip_scale=None,"
+      " Tensor? sched=None, Tensor(h!)? lr_out=None, bool nesterov=False, bool decay=False) -> ()");
   m.def(
       "apply_gradients_group(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor?[] s1, Tensor?[] s2,"
       " float[] hyper, Tensor?[] beta_pow, Tensor?[] global_step, int[] gs_inc, Tensor[] done, Tensor[] blob,"
-      " int[] nseg, int[] nwork, Tensor?[]? clip_scale=None) -> ()");
+      " int[] nseg, int[] nwork, Tensor?[]? clip_scale=None, Tensor?[]? sched=None, Tensor?[]? lr_out=None,"
+      " int[]? nesterov=None, int[]? decay=None) -> ()");
   m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
         " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
   m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
@@ -1558,5 +1631,6 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
 
 TORCH_LIBRARY_IMPL(dtfe, CompositeExplicitAutograd, m) {
   m.impl("opt_pack", &opt_pack);
+  m.impl("lr_schedule_pack", &lr_schedule_pack);
   m.impl("gan_head_ws_floats", &gan_head_ws_floats);
 }

@@ -13,6 +13,7 @@ enum OptKind : int { OPT_SGD = 0, OPT_MOMENTUM = 1, OPT_ADAM = 2, OPT_RMSPROP = 
 struct OptSeg {
   long off;
   int R, T, C;
+  float wd;    // coupled L2 weight decay of this segment (0: none); sits in the former padding after C
   bf16* w16;   // natural-layout bf16 working copy (nullable)
   bf16* wt16;  // transposed bf16 working copy (nullable)
   // second destinations of the updated values (nullable): a ps writes the requesting worker's
@@ -23,6 +24,8 @@ struct OptSeg {
   float* pb;
 };
 
+static_assert(sizeof(OptSeg) == 64, "OptSeg: wd fills the padding, the plan blobs keep their layout");
+
 // Work item: kind 0 = flat range [start, start+count) of segment seg;
 // kind 1 = 64x64 tile (r0, c0) of tap t of segment seg (transpose path).
 struct OptWork {
@@ -32,6 +35,42 @@ struct OptWork {
 
 // An optimizer plan is one device blob: nseg OptSeg, then the OptWork items at the next 256-B boundary
 inline size_t opt_blob_work_offset(size_t nseg) { return (nseg * sizeof(OptSeg) + 255) / 256 * 256; }
+
+// A learning-rate schedule evaluated on the device from *global_step (OptArgs::sched).  Integer compares
+// and fp32 +, -, * only, no contraction: a numpy-float32 host mirror (ops.lr_schedule_value) gives the
+// same bits.  The reciprocals are rounded to float32 on the host.
+constexpr int LR_MAX_BOUNDS = 8;
+enum LrKind : int { LR_CONSTANT = 0, LR_PIECEWISE = 1, LR_LINEAR = 2 };
+struct LrSchedule {
+  int kind;
+  int nb;                          // piecewise: boundaries in use
+  int bounds[LR_MAX_BOUNDS];       // strictly increasing
+  float values[LR_MAX_BOUNDS + 1];
+  float lr, end;                   // constant: lr; linear: from lr to end over decay_steps steps
+  int decay_steps; float inv_decay;
+  int warmup; float inv_warmup;    // warmup > 0: the rate times (step + 1) / warmup while step < warmup
+};
+static_assert(sizeof(LrSchedule) == 25 * 4, "LrSchedule: 25 four-byte fields, no padding");
+
+// tf.train.piecewise_constant (values[i] for b[i-1] < step <= b[i]) / tf.train.polynomial_decay with
+// power 1 and no cycling, each under an optional linear warm-up
+// Branch-free over the boundaries (they increase, so the last one passed decides): nothing here is
+// loaded depending on step, the struct and the step can be in flight together.
+__host__ __device__ __forceinline__ float lr_schedule_eval(const LrSchedule& s, int step) {
+#pragma clang fp contract(off)
+  float v = s.lr;
+  if (s.kind == LR_PIECEWISE) {
+    v = s.values[0];
+#pragma unroll
+    for (int i = 0; i < LR_MAX_BOUNDS; ++i)
+      if (i < s.nb && step > s.bounds[i]) v = s.values[i + 1];
+  } else if (s.kind == LR_LINEAR) {
+    const float t = (float)(step < s.decay_steps ? step : s.decay_steps);
+    v = (s.lr - s.end) * (1.f - t * s.inv_decay) + s.end;
+  }
+  if (step < s.warmup) v = v * ((float)(step + 1) * s.inv_warmup);
+  return v;
+}
 
 struct OptArgs {
   int kind;
@@ -59,6 +98,12 @@ struct OptArgs {
   // optional device scalar multiplied into gscale (nullable): the scale of a global-norm clip
   // (gradnorm.h, launch_grad_sumsq's out[1]).  Null: the arithmetic is exactly gscale's
   const float* clip_scale;
+  // optional learning-rate schedule (nullable): every workgroup evaluates it at *global_step when it
+  // starts and uses the result in place of lr.  Null: lr, and the arithmetic is exactly as without it
+  const LrSchedule* sched;
+  float* lr_out;            // nullable: the last workgroup stores the rate this launch used
+  int nesterov;             // OPT_MOMENTUM: TF1 ApplyMomentum's use_nesterov form
+  int decay;                // 1: some segment has wd != 0 (the kernels' weight-decay instantiation)
 };
 // points a.segs / a.work into a plan blob of nseg segments
 inline void opt_blob_plan(const void* blob, size_t nseg, OptArgs& a) {

@@ -12,6 +12,9 @@
 //               v2 = b2 v2 + (1-b2) g^2; v -= lr_t * m / (sqrt(v2) + eps)
 //   RMSProp   : ms = rho ms + (1-rho) g^2 ; mom = mu mom + lr g / sqrt(ms + eps); v -= mom
 //               (ms slot initialised to ONES by the host)
+//   Nesterov  : a = m*a + g ; v -= g*lr + (a*m)*lr            (ApplyMomentum, use_nesterov)
+// Optional, all inside the same launch: lr from a schedule evaluated at global_step
+// (OptArgs::sched), and a coupled L2 term per segment, g = g*scale + wd*v (OptSeg::wd).
 //
 // Memory-bound: the flat path moves 4 elements per thread per iteration with
 // 16-byte loads/stores of every stream (p, g, slots) and 8-byte bf16 stores.
@@ -19,32 +22,56 @@
 
 namespace dtfe {
 
-template <int KIND>
-__device__ __forceinline__ float upd(const OptArgs& a, float lr_t, float v, float g, float& s1, float& s2) {
+// the rates of one launch: lr is the host's a.lr or the schedule's value at *global_step; lr_t is what
+// Adam multiplies with (lr with the bias correction folded in), lr itself for the other kinds
+struct OptRate {
+  float lr, lr_t;
+};
+
+template <int KIND, bool NAG>
+__device__ __forceinline__ float upd(const OptArgs& a, OptRate rt, float v, float g, float& s1, float& s2) {
   // no multiply-add contraction: the rounding of every update must not depend on how a kernel
   // instantiation's instruction selection happened to fuse it (a grouped launch of several
   // optimizers and separate launches must agree bitwise)
 #pragma clang fp contract(off)
   if constexpr (KIND == OPT_SGD) {
-    return v - a.lr * g;
+    return v - rt.lr * g;
   } else if constexpr (KIND == OPT_MOMENTUM) {
+    if constexpr (NAG) {
+      if (a.nesterov) {  // TF1 ApplyMomentum, use_nesterov: a = a m + g ; v -= g lr + a m lr
+        s1 = s1 * a.momentum + g;
+        return v - (g * rt.lr + s1 * a.momentum * rt.lr);
+      }
+    }
     s1 = s1 * a.momentum + g;
-    return v - a.lr * s1;
+    return v - rt.lr * s1;
   } else if constexpr (KIND == OPT_ADAM) {
-    return tf1_adam(v, g, s1, s2, lr_t, a.beta1, a.beta2, a.eps);
+    return tf1_adam(v, g, s1, s2, rt.lr_t, a.beta1, a.beta2, a.eps);
   } else {
     s1 = s1 * a.rho + (1.f - a.rho) * g * g;
-    s2 = s2 * a.momentum + a.lr * g / sqrtf(s1 + a.eps);
+    s2 = s2 * a.momentum + rt.lr * g / sqrtf(s1 + a.eps);
     return v - s2;
   }
 }
 
-template <int KIND>
-__device__ __forceinline__ float update_one(const OptArgs& a, float lr_t, long i, float g) {
+// the gradient an update sees: g * gs (gs: the host's scale times a clip's), plus - in the weight-decay
+// instantiation, for a segment with wd != 0 - the coupled L2 term wd * p, added after the clip scale
+// as torch.optim.SGD(weight_decay=) adds it after clip_grad_norm_.  A select, not "+ 0 * p": a segment
+// without decay keeps its -0 and does not meet a non-finite parameter.
+template <bool WD>
+__device__ __forceinline__ float scaled_grad(float g, float gs, float wd, float p) {
+#pragma clang fp contract(off)
+  const float x = g * gs;
+  if constexpr (WD) return wd != 0.f ? x + wd * p : x;
+  return x;
+}
+
+template <int KIND, bool NAG>
+__device__ __forceinline__ float update_one(const OptArgs& a, OptRate rt, long i, float p, float g) {
   float s1 = 0.f, s2 = 0.f;
   if (KIND != OPT_SGD) s1 = a.s1[i];
   if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) s2 = a.s2[i];
-  const float v = upd<KIND>(a, lr_t, a.p[i], g, s1, s2);
+  const float v = upd<KIND, NAG>(a, rt, p, g, s1, s2);
   a.p[i] = v;
   if (KIND != OPT_SGD) a.s1[i] = s1;
   if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) a.s2[i] = s2;
@@ -52,8 +79,8 @@ __device__ __forceinline__ float update_one(const OptArgs& a, float lr_t, long i
 }
 
 template <bool G16>
-__device__ __forceinline__ float load_grad(const OptArgs& a, float gs, long i) {
-  return (G16 ? bf2f(a.g16[i]) : a.g[i]) * gs;
+__device__ __forceinline__ float load_grad(const OptArgs& a, long i) {
+  return G16 ? bf2f(a.g16[i]) : a.g[i];
 }
 
 // the updated values' extra destinations: bf16 copies (w16, the ps reply's w16b) and the fp32 copy pb
@@ -66,8 +93,9 @@ __device__ __forceinline__ void store_copies(const f32x4_t& p, bf16* w16, bf16* 
   if (pb) *reinterpret_cast<f32x4_t*>(pb) = p;
 }
 
-template <int KIND, bool G16>
-__device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, float gs, long i, bf16* w16, bf16* w16b, float* pb) {
+template <int KIND, bool G16, bool WD, bool NAG>
+__device__ __forceinline__ void update_vec4(const OptArgs& a, OptRate rt, float gs, float wd, long i, bf16* w16, bf16* w16b,
+                                            float* pb) {
   f32x4_t g;
   if constexpr (!G16) {
     g = *reinterpret_cast<const f32x4_t*>(a.g + i);
@@ -83,7 +111,7 @@ __device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, float 
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float x1 = s1[j], x2 = s2[j];
-    p[j] = upd<KIND>(a, lr_t, p[j], g[j] * gs, x1, x2);
+    p[j] = upd<KIND, NAG>(a, rt, p[j], scaled_grad<WD>(g[j], gs, wd, p[j]), x1, x2);
     s1[j] = x1;
     s2[j] = x2;
   }
@@ -95,8 +123,9 @@ __device__ __forceinline__ void update_vec4(const OptArgs& a, float lr_t, float 
 
 // U vec4 updates at i, i+1024, ... (one workgroup-wide stride apart): every load is issued
 // before the first update, so each thread keeps U x (3-4) 16-B loads in flight
-template <int KIND, int U, bool G16>
-__device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, float gs, long i, bf16* w16, bf16* w16b, float* pb) {
+template <int KIND, int U, bool G16, bool WD, bool NAG>
+__device__ __forceinline__ void update_vec4x(const OptArgs& a, OptRate rt, float gs, float wd, long i, bf16* w16, bf16* w16b,
+                                             float* pb) {
   f32x4_t g[U], p[U], s1[U], s2[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -119,7 +148,7 @@ __device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, float
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float x1 = s1[u][j], x2 = s2[u][j];
-      p[u][j] = upd<KIND>(a, lr_t, p[u][j], g[u][j] * gs, x1, x2);
+      p[u][j] = upd<KIND, NAG>(a, rt, p[u][j], scaled_grad<WD>(g[u][j], gs, wd, p[u][j]), x1, x2);
       s1[u][j] = x1;
       s2[u][j] = x2;
     }
@@ -132,10 +161,11 @@ __device__ __forceinline__ void update_vec4x(const OptArgs& a, float lr_t, float
 
 // One optimizer's share of a launch: workgroups bid = 0..nblk-1 of the grid (the whole grid for a
 // plain launch, a contiguous range of it for a grouped one).
-template <int KIND, bool G16>
-__device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk, bf16 (&tile)[64][66]) {
-  float lr_t = a.lr;
-  if (KIND == OPT_ADAM) lr_t = tf1_adam_lr(a.lr, a.beta_pow);
+// lr: the launch's learning rate (launch_rate).
+template <int KIND, bool G16, bool WD, bool NAG>
+__device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid, int nblk, bf16 (&tile)[64][66]) {
+  OptRate rt{lr, lr};
+  if (KIND == OPT_ADAM) rt.lr_t = tf1_adam_lr(lr, a.beta_pow);
   // the gradient scale of this launch: the host's, times the device scalar of a global-norm clip
   // (grad_sumsq_kernel's out[1], written by the launch before this one on the stream)
   const float gs = a.clip_scale ? a.gscale * *a.clip_scale : a.gscale;
@@ -165,12 +195,13 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
       auto at16 = [&](bf16* q, long jj) { return q ? q + w.start + jj : nullptr; };
       auto at32 = [&](float* q, long jj) { return q ? q + w.start + jj : nullptr; };
       for (; j + 3 * 1024 < n4; j += 4 * 1024)  // 4 independent vec4 updates in flight per thread
-        update_vec4x<KIND, 4, G16>(a, lr_t, gs, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+        update_vec4x<KIND, 4, G16, WD, NAG>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
       for (; j < n4; j += 256 * 4)
-        update_vec4<KIND, G16>(a, lr_t, gs, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+        update_vec4<KIND, G16, WD, NAG>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
       for (long j = n4 + threadIdx.x; j < w.count; j += 256) {
         const long li = w.start + j, i = sg.off + li;
-        const float v = update_one<KIND>(a, lr_t, i, load_grad<G16>(a, gs, i));
+        const float p = a.p[i];
+        const float v = update_one<KIND, NAG>(a, rt, i, p, scaled_grad<WD>(load_grad<G16>(a, i), gs, sg.wd, p));
         if (sg.w16) sg.w16[li] = f2bf(v);
         if (sg.w16b) sg.w16b[li] = f2bf(v);
         if (sg.pb) sg.pb[li] = v;
@@ -188,8 +219,8 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
         // out-of-tile lanes load the segment's first element (never stored): no branches here
         const bool ok = r < sg.R && c < sg.C;
         const long i = sg.off + (ok ? ((long)r * sg.T + w.t) * sg.C + c : 0);
-        gv[u] = load_grad<G16>(a, gs, i);
         pv[u] = a.p[i];
+        gv[u] = scaled_grad<WD>(load_grad<G16>(a, i), gs, sg.wd, pv[u]);
         s1v[u] = KIND != OPT_SGD ? a.s1[i] : 0.f;
         s2v[u] = (KIND == OPT_ADAM || KIND == OPT_RMSPROP) ? a.s2[i] : 0.f;
       }
@@ -199,7 +230,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
         if (r < sg.R && c < sg.C) {
           const long li = ((long)r * sg.T + w.t) * sg.C + c, i = sg.off + li;
           float x1 = s1v[u], x2 = s2v[u];
-          const float v = upd<KIND>(a, lr_t, pv[u], gv[u], x1, x2);
+          const float v = upd<KIND, NAG>(a, rt, pv[u], gv[u], x1, x2);
           a.p[i] = v;
           if (KIND != OPT_SGD) a.s1[i] = x1;
           if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) a.s2[i] = x2;
@@ -224,6 +255,28 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, int bid, int nblk,
   }
 }
 
+// The learning rate of a launch, read by every workgroup before its first item: the host's a.lr, or the
+// schedule's value at the global step the launch starts from.  The last workgroup advances the step
+// only after every workgroup has finished its items, so all of a launch's workgroups read the same
+// step here.  The whole struct is loaded before the step is waited for - one round trip to memory for
+// both, not a chain of loads that depend on the step.
+// Out of line: cold code that stays out of the update loops' register allocation (inlined it cost the
+// plain SGD kernel 4 VGPRs, a wave of occupancy).  A call passes pointers in vector registers, so the
+// schedule's address is made scalar again (readfirstlane of its halves): the struct arrives by scalar loads.
+__device__ __noinline__ float scheduled_rate(const LrSchedule* sched, int32_t* global_step) {
+  const uint64_t addr = reinterpret_cast<uint64_t>(sched);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
+  const LrSchedule s = *reinterpret_cast<const LrSchedule*>(((uint64_t)hi << 32) | lo);
+  const int step = __hip_atomic_load(global_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return lr_schedule_eval(s, __builtin_amdgcn_readfirstlane(step));
+}
+__device__ __forceinline__ float launch_rate(const OptArgs& a) {
+  if (!a.sched) return a.lr;
+  // wave-uniform, and told so (readfirstlane): the rate stays in a scalar register like the host's a.lr
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scheduled_rate(a.sched, a.global_step))));
+}
+
 // the ps reply words (ps_link.h PsWord: REP_GS 9, REP_VER 10, REP_STALE 11, REP_SEQ 8 last) into
 // the worker's slot of the host-mapped shared page: system-scope relaxed stores (they go to the
 // page, no cache holds them), the sequence number only after the others have completed - no
@@ -240,10 +293,14 @@ __device__ __forceinline__ void publish_reply(const OptArgs& a) {
   __hip_atomic_store(slot + 8, a.rep_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int KIND>
+// WD: the weight-decay instantiation, launched only when some segment decays (OptArgs::decay); NAG: the
+// one with the Nesterov branch (OptArgs::nesterov).  A launch with neither runs the kernel, and the
+// arithmetic, it ran before there was either
+template <int KIND, bool WD, bool NAG>
 __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, bf16 (&tile)[64][66]) {
-  if (a.g) apply_items<KIND, false>(a, bid, nblk, tile);
-  else apply_items<KIND, true>(a, bid, nblk, tile);
+  const float lr = launch_rate(a);
+  if (a.g) apply_items<KIND, false, WD, NAG>(a, lr, bid, nblk, tile);
+  else apply_items<KIND, true, WD, NAG>(a, lr, bid, nblk, tile);
   // last workgroup: advance the non-slot scalars.  Every thread read them at its start and
   // used the value; after the barrier one lane takes a ticket (relaxed agent atomics - nothing
   // is handed between workgroups, so no fences) and the last arriver updates them.
@@ -254,6 +311,8 @@ __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, 
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t prev = __hip_atomic_fetch_add(a.done_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the rate this launch used, for logging: stored before the step it was computed from advances
+    if (prev == (uint32_t)nblk - 1 && a.lr_out) *a.lr_out = lr;
     if (prev == (uint32_t)nblk - 1 && !a.skip_advance) {
       if (KIND == OPT_ADAM) {
         a.beta_pow[0] *= a.beta1;
@@ -268,21 +327,23 @@ __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, 
   }
 }
 
-template <int KIND>
+template <int KIND, bool WD, bool NAG>
 __global__ __launch_bounds__(256) void apply_gradients_kernel(OptArgs a) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
-  apply_body<KIND>(a, blockIdx.x, gridDim.x, tile);
+  apply_body<KIND, WD, NAG>(a, blockIdx.x, gridDim.x, tile);
 }
 
 // Several optimizers of one kind in ONE launch (the GAN's two Adams over disjoint var lists):
 // workgroup ranges [first[i], first[i + 1]) run optimizer i; each keeps its own done counter,
 // beta powers and global-step increment, exactly as separate launches would.
-template <int KIND>
+// Not for optimizers with a schedule that share a global step: one optimizer's last workgroup may
+// advance the step before another's workgroups have read it (launch_apply_gradients_group refuses).
+template <int KIND, bool WD, bool NAG>
 __global__ __launch_bounds__(256) void apply_gradients_group_kernel(OptGroup g) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
   int i = 0;
   while (i + 1 < g.n && (int)blockIdx.x >= g.first[i + 1]) ++i;
-  apply_body<KIND>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
+  apply_body<KIND, WD, NAG>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
 }
 
 __device__ __forceinline__ void advance_one(const OptArgs& a) {
@@ -318,23 +379,55 @@ static int apply_blocks(const OptArgs& a) {
   return blocks < 1 ? 1 : blocks;
 }
 
+static void check_sched(const OptArgs& a) {
+  if (a.sched && !a.global_step) throw std::runtime_error("apply_gradients: a learning-rate schedule needs a global_step");
+  if (a.nesterov && a.kind != OPT_MOMENTUM)
+    throw std::runtime_error("apply_gradients: nesterov is for the momentum optimizer");
+}
+
+// the instantiation of a launch: WD when some segment decays, NAG (momentum only) when some optimizer
+// of the launch uses Nesterov momentum; neither: the kernel as it was before either existed
+template <bool WD, bool NAG>
+static void launch_group(const OptGroup& g, dim3 grid, hipStream_t s) {
+  const dim3 blk(256);
+  switch (g.o[0].kind) {
+    case OPT_SGD: hipLaunchKernelGGL((apply_gradients_group_kernel<OPT_SGD, WD, false>), grid, blk, 0, s, g); break;
+    case OPT_MOMENTUM: hipLaunchKernelGGL((apply_gradients_group_kernel<OPT_MOMENTUM, WD, NAG>), grid, blk, 0, s, g); break;
+    case OPT_ADAM: hipLaunchKernelGGL((apply_gradients_group_kernel<OPT_ADAM, WD, false>), grid, blk, 0, s, g); break;
+    default: hipLaunchKernelGGL((apply_gradients_group_kernel<OPT_RMSPROP, WD, false>), grid, blk, 0, s, g); break;
+  }
+}
+
+template <bool WD, bool NAG>
+static void launch_one(const OptArgs& a, int blocks, hipStream_t s) {
+  const dim3 grid(blocks), blk(256);
+  switch (a.kind) {
+    case OPT_SGD: hipLaunchKernelGGL((apply_gradients_kernel<OPT_SGD, WD, false>), grid, blk, 0, s, a); break;
+    case OPT_MOMENTUM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG>), grid, blk, 0, s, a); break;
+    case OPT_ADAM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_ADAM, WD, false>), grid, blk, 0, s, a); break;
+    default: hipLaunchKernelGGL((apply_gradients_kernel<OPT_RMSPROP, WD, false>), grid, blk, 0, s, a); break;
+  }
+}
+
 void launch_apply_gradients_group(const OptArgs* o, int n, hipStream_t s) {
   if (n < 1 || n > OPT_GROUP_MAX) throw std::runtime_error("apply_gradients_group: 1..4 optimizers");
   OptGroup g{};
   g.n = n;
   g.first[0] = 0;
+  bool decay = false, nag = false;
   for (int i = 0; i < n; ++i) {
     if (o[i].kind != o[0].kind) throw std::runtime_error("apply_gradients_group: one optimizer kind per launch");
+    check_sched(o[i]);
+    if (o[i].sched && n > 1)
+      throw std::runtime_error("apply_gradients_group: an optimizer with a schedule takes a launch of its own");
+    decay = decay || o[i].decay;
+    nag = nag || o[i].nesterov;
     g.o[i] = o[i];
     g.first[i + 1] = g.first[i] + apply_blocks(o[i]);
   }
   const dim3 grid(g.first[n]);
-  switch (o[0].kind) {
-    case OPT_SGD: hipLaunchKernelGGL(apply_gradients_group_kernel<OPT_SGD>, grid, dim3(256), 0, s, g); break;
-    case OPT_MOMENTUM: hipLaunchKernelGGL(apply_gradients_group_kernel<OPT_MOMENTUM>, grid, dim3(256), 0, s, g); break;
-    case OPT_ADAM: hipLaunchKernelGGL(apply_gradients_group_kernel<OPT_ADAM>, grid, dim3(256), 0, s, g); break;
-    default: hipLaunchKernelGGL(apply_gradients_group_kernel<OPT_RMSPROP>, grid, dim3(256), 0, s, g); break;
-  }
+  if (decay) nag ? launch_group<true, true>(g, grid, s) : launch_group<true, false>(g, grid, s);
+  else nag ? launch_group<false, true>(g, grid, s) : launch_group<false, false>(g, grid, s);
 }
 
 void launch_opt_advance(const OptArgs& a, hipStream_t s) {
@@ -350,15 +443,10 @@ void launch_opt_advance_reply(const OptArgs* a, int n, hipStream_t s) {
 }
 
 void launch_apply_gradients(const OptArgs& a, hipStream_t s) {
+  check_sched(a);
   const int blocks = apply_blocks(a);
-  switch (a.kind) {
-    case OPT_SGD: hipLaunchKernelGGL(apply_gradients_kernel<OPT_SGD>, dim3(blocks), dim3(256), 0, s, a); break;
-    case OPT_MOMENTUM:
-      hipLaunchKernelGGL(apply_gradients_kernel<OPT_MOMENTUM>, dim3(blocks), dim3(256), 0, s, a);
-      break;
-    case OPT_ADAM: hipLaunchKernelGGL(apply_gradients_kernel<OPT_ADAM>, dim3(blocks), dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(apply_gradients_kernel<OPT_RMSPROP>, dim3(blocks), dim3(256), 0, s, a); break;
-  }
+  if (a.decay) a.nesterov ? launch_one<true, true>(a, blocks, s) : launch_one<true, false>(a, blocks, s);
+  else a.nesterov ? launch_one<false, true>(a, blocks, s) : launch_one<false, false>(a, blocks, s);
 }
 
 }  // namespace dtfe

@@ -70,6 +70,8 @@ class ModelDef:
     default_batch: int = 128
     default_steps: int = 1000
     needs_labels: bool = True
+    # the variables --weight_decay applies to; None: the model takes neither --weight_decay nor --nesterov
+    decay_vars: list | None = None
     # compute dtypes the model's step program implements (--dtype); the first is the default
     dtypes: tuple = ("fp32",)
     dtype: str | None = None

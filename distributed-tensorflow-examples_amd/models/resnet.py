@@ -659,6 +659,9 @@ class ResNetModel(ModelDef):
         trainable = [n for n in creation if not n.endswith(("/moving_mean", "/moving_variance"))]
         self.opt_groups = [(OptimizerConfig(kind="momentum", lr=lr, momentum=0.9), trainable,
                             ("beta1_power", "beta2_power"))]
+        # the variables --weight_decay decays: conv and dense kernels - not batch-norm gamma / beta, not
+        # the dense bias (the usual CIFAR-10 recipe)
+        self.decay_vars = [n for n in trainable if n.endswith("/kernel")]
         self.image, self.channels, self.num_classes = ARCHS[arch]
 
     def num_params(self, trainable_only=True):

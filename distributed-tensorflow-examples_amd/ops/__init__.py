@@ -29,7 +29,7 @@ __all__ = [
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
-    "augment_rows", "augment_draws", "AUG_SALT",
+    "augment_rows", "augment_draws", "AUG_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -716,19 +716,93 @@ def gemm_group(anchor):
 
 
 # --------------------------------------------------------------- optimizer
-def opt_pack(segs, work, device_like):
-    return require().opt_pack(segs, work, device_like)
+def opt_pack(segs, work, device_like, wd=None):
+    """``wd``: the coupled L2 weight decay of each segment (a sequence of nseg floats); None = no decay."""
+    if wd is None:
+        return require().opt_pack(segs, work, device_like)
+    return require().opt_pack(segs, work, device_like, torch.tensor([float(x) for x in wd], dtype=torch.float32))
 
 
 def apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
-                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0, clip_scale=None):
+                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0, clip_scale=None,
+                    sched=None, lr_out=None, nesterov=False, decay=False):
     """The launch's items of the var-list segments in bit mask ``wait_segs`` wait (on the device) until
     ``wait_done`` exceeds ``wait_seen`` - a gradient produced on another stream that signals with
     epoch_signal(wait_done) instead of a stream join; the launch's last workgroup advances ``wait_seen``.
-    ``clip_scale``: a device float32 scalar multiplied into ``gscale`` by the kernel (grad_sumsq's scale)."""
+    ``clip_scale``: a device float32 scalar multiplied into ``gscale`` by the kernel (grad_sumsq's scale).
+    ``sched``: the blob of lr_schedule_pack - the kernel evaluates it at ``global_step`` and uses the result
+    in place of ``lr``; ``lr_out``: a device float32 scalar that receives the rate the launch used.
+    ``nesterov``: TF1 ApplyMomentum's use_nesterov form (momentum only).  ``decay``: the plan was packed
+    with a non-zero weight decay on some segment (opt_pack's ``wd``); without it the decay is ignored."""
     require().apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow,
                               global_step, gs_inc, done, blob, nseg, nwork, wait_done, wait_seen, wait_segs,
-                              clip_scale)
+                              clip_scale, sched, lr_out, bool(nesterov), bool(decay))
+
+
+# learning-rate schedules (csrc/kernels/optim.h LrSchedule / lr_schedule_eval)
+LR_CONSTANT, LR_PIECEWISE, LR_LINEAR = 0, 1, 2
+LR_MAX_BOUNDS = 8
+
+
+def lr_schedule_spec(lr=0.0, boundaries=(), values=(), decay_steps=0, end=0.0, warmup_steps=0):
+    """The validated description of a schedule, as a dict of float32 / int fields:
+    ``boundaries`` / ``values`` - tf.train.piecewise_constant (``values[i]`` while
+    ``boundaries[i-1] < step <= boundaries[i]``, the last value beyond); ``decay_steps`` / ``end`` -
+    tf.train.polynomial_decay with power 1 and no cycling, from ``lr`` to ``end``; neither - the constant
+    ``lr``.  ``warmup_steps`` W multiplies the rate by ``(step + 1) / W`` while ``step < W``.
+    The reciprocals are rounded to float32 here, once: kernel and mirror multiply by the same value."""
+    f = np.float32
+    boundaries, values = [int(b) for b in boundaries], [float(v) for v in values]
+    decay_steps, warmup_steps = int(decay_steps or 0), int(warmup_steps or 0)
+    if (boundaries or values) and decay_steps:
+        raise ValueError("lr schedule: piecewise-constant (boundaries/values) and linear decay (decay_steps) "
+                         "are mutually exclusive")
+    if boundaries or values:
+        if len(values) != len(boundaries) + 1:
+            raise ValueError("lr schedule: %d boundaries need %d values, got %d"
+                             % (len(boundaries), len(boundaries) + 1, len(values)))
+        if not 1 <= len(boundaries) <= LR_MAX_BOUNDS:
+            raise ValueError("lr schedule: 1 to %d boundaries, got %d" % (LR_MAX_BOUNDS, len(boundaries)))
+        if any(b < 0 or b >= 2 ** 31 for b in boundaries) or any(y <= x for x, y in zip(boundaries, boundaries[1:])):
+            raise ValueError("lr schedule: boundaries must be strictly increasing steps, got %r" % (boundaries,))
+        kind = LR_PIECEWISE
+    elif decay_steps:
+        if not 1 <= decay_steps < 2 ** 31:
+            raise ValueError("lr schedule: decay_steps must be >= 1, got %r" % (decay_steps,))
+        kind = LR_LINEAR
+    else:
+        kind = LR_CONSTANT
+    if not 0 <= warmup_steps < 2 ** 31:
+        raise ValueError("lr schedule: warmup_steps must be >= 0, got %r" % (warmup_steps,))
+    return {"kind": kind, "bounds": boundaries, "values": [f(v) for v in values], "lr": f(lr), "end": f(end),
+            "decay_steps": decay_steps, "inv_decay": f(1) / f(decay_steps) if decay_steps else f(0),
+            "warmup": warmup_steps, "inv_warmup": f(1) / f(warmup_steps) if warmup_steps else f(0)}
+
+
+def lr_schedule_value(spec, step):
+    """The rate at ``step`` as numpy float32: the host mirror of the kernel's lr_schedule_eval, operation
+    for operation (integer compares; fp32 +, -, *, each rounded once), so the two agree bit for bit."""
+    f = np.float32
+    step = int(step)
+    v = spec["lr"]
+    if spec["kind"] == LR_PIECEWISE:
+        i = 0
+        while i < len(spec["bounds"]) and step > spec["bounds"][i]:
+            i += 1
+        v = spec["values"][i]
+    elif spec["kind"] == LR_LINEAR:
+        t = f(min(step, spec["decay_steps"]))
+        v = f(f(spec["lr"] - spec["end"]) * f(f(1) - f(t * spec["inv_decay"]))) + spec["end"]
+    if step < spec["warmup"]:
+        v = f(v * f(f(step + 1) * spec["inv_warmup"]))
+    return f(v)
+
+
+def lr_schedule_pack(spec, device_like):
+    """The device struct (a uint8 blob) of a lr_schedule_spec, for apply_gradients' ``sched``."""
+    return require().lr_schedule_pack(spec["kind"], spec["bounds"], [float(v) for v in spec["values"]],
+                                      float(spec["lr"]), float(spec["end"]), spec["decay_steps"],
+                                      float(spec["inv_decay"]), spec["warmup"], float(spec["inv_warmup"]), device_like)
 
 
 GRAD_CHUNK_MAX = 8192  # csrc/kernels/gradnorm.h

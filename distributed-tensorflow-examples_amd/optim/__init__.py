@@ -155,6 +155,23 @@ class OptimizerConfig:
     name: str = field(default="")
     # tf.clip_by_global_norm over the optimizer's var list before the update; 0 = off (the reference)
     clip_norm: float = 0.0
+    # learning-rate schedule, a function of global_step evaluated inside the fused apply (all off = the
+    # constant lr): tf.train.piecewise_constant (lr_boundaries / lr_values) or linear decay from lr to
+    # lr_end over lr_decay_steps (tf.train.polynomial_decay, power 1), either under a linear warm-up
+    lr_boundaries: tuple = ()
+    lr_values: tuple = ()
+    lr_decay_steps: int = 0
+    lr_end: float = 0.0
+    lr_warmup_steps: int = 0
+    # coupled L2 weight decay (g += weight_decay * p, after the clip scale) on the variables decay_vars
+    # (None: every variable of the var list)
+    weight_decay: float = 0.0
+    decay_vars: tuple | None = None
+    # momentum only: TF1 ApplyMomentum's use_nesterov
+    nesterov: bool = False
+
+    def has_schedule(self):
+        return bool(self.lr_boundaries or self.lr_values or self.lr_decay_steps or self.lr_warmup_steps)
 
     def resolved_eps(self):
         if self.eps is not None:
@@ -233,14 +250,52 @@ class Optimizer:
             if cfg.kind == "adam" else None
         self.done = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._blob = None
+        self._init_recipe()
         if self.device.type == "cuda":
             self._build_plan()
+            if self.lr_spec is not None:
+                self._sched = ops.lr_schedule_pack(self.lr_spec, params.master)
         # global-norm clipping (cfg.clip_norm > 0): the norm kernel's chunk plan, scratch and its two
         # results clip_out = [norm, scale]; the apply reads the scale from the device.  No state to save.
         self.clip_norm = float(getattr(cfg, "clip_norm", 0.0) or 0.0)
         if self.clip_norm < 0:
             raise ValueError("clip_norm must be >= 0 (0 = no clipping), got %r" % (cfg.clip_norm,))
         self.clip = GlobalNormClip(params, self.var_list, self.clip_norm) if self.clip_norm > 0 else None
+
+    def _init_recipe(self):
+        """Schedule, weight decay and Nesterov of the config, validated; all of it off by default."""
+        cfg = self.cfg
+        self.lr_spec, self._sched, self._lr_out = None, None, None
+        if cfg.has_schedule():
+            if self.global_step is None:
+                raise ValueError("Optimizer: a learning-rate schedule is a function of global_step - pass one")
+            self.lr_spec = ops.lr_schedule_spec(cfg.lr, cfg.lr_boundaries, cfg.lr_values, cfg.lr_decay_steps,
+                                                cfg.lr_end, cfg.lr_warmup_steps)
+            self._lr_out = torch.full((1,), float(ops.lr_schedule_value(self.lr_spec, 0)), dtype=torch.float32,
+                                      device=self.device)
+        self.nesterov = bool(cfg.nesterov)
+        if self.nesterov and cfg.kind != "momentum":
+            raise ValueError("Optimizer: nesterov is an option of the momentum optimizer, not of %r" % (cfg.kind,))
+        wd = float(cfg.weight_decay or 0.0)
+        if wd < 0:
+            raise ValueError("weight_decay must be >= 0 (0 = none), got %r" % (cfg.weight_decay,))
+        decay_vars = self.var_list if cfg.decay_vars is None else list(cfg.decay_vars)
+        unknown = [n for n in decay_vars if n not in self.var_list]
+        if wd > 0 and unknown:
+            raise ValueError("Optimizer: decay_vars %r are not in the var list" % (unknown,))
+        # per variable of the var list; float32 as the kernel holds it
+        self.wd = [wd if wd > 0 and n in decay_vars else 0.0 for n in self.var_list]
+        self.decay = any(w != 0 for w in self.wd)
+
+    @property
+    def current_lr(self):
+        """The rate the last step used (before any step: the rate of step 0) as a 1-element device tensor
+        - read it on the host only when it is wanted; None without a schedule (the rate is cfg.lr)."""
+        return self._lr_out
+
+    def _recipe_args(self):
+        return dict(sched=self._sched, lr_out=self._lr_out if self._sched is not None else None,
+                    nesterov=self.nesterov, decay=self.decay)
 
     # ---- plan of work items for the fused kernel
     def _build_plan(self, chunk: int = 0):
@@ -277,8 +332,9 @@ class Optimizer:
             # LDS transpose, scattered stores); dispatched last they were the launch's tail
             work.sort(key=lambda w: -w[0])
         self.nseg, self.nwork = len(segs), len(work)
+        self._tables = (segs, work)  # what the blob was packed from (tests repack it)
         self._blob = ops.opt_pack(torch.tensor(segs, dtype=torch.int64), torch.tensor(work, dtype=torch.int64),
-                                  self.P.master)
+                                  self.P.master, self.wd if self.decay else None)
 
     def _wait_mask(self, names) -> int:  # the kernel's wait_segs: 32 bits of var_list indices
         idx = [self.var_list.index(n) if n in self.var_list else -1 for n in names]
@@ -316,7 +372,7 @@ class Optimizer:
         if self.device.type == "cuda":
             ops.apply_gradients(self.kind, self.P.master, grad, grad16, gscale, self.s1, self.s2, *self._hyper(),
                                 self.beta_pow, self.global_step, gs_inc, self.done, self._blob, self.nseg,
-                                self.nwork, *wait, clip_scale=clip)
+                                self.nwork, *wait, clip_scale=clip, **self._recipe_args())
             return
         self._step_cpu(grad if grad is not None else grad16.float(), gscale, gs_inc, clip)
 
@@ -327,7 +383,13 @@ class Optimizer:
         launch (each keeps its own beta powers / global-step increment); the math equals
         calling ``step`` on each in order."""
         kinds = {o.kind for o in opts}
-        if len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and all(o.device.type == "cuda" for o in opts):
+        # Optimizers with a schedule take the sequential path: in the grouped launch one optimizer's last
+        # workgroup may advance the shared global_step before another optimizer's workgroups have read
+        # it, and those would evaluate their schedule one step ahead.  One launch each keeps every read
+        # of the step before the launch that advances it (stream order).
+        scheduled = any(o.lr_spec is not None for o in opts)
+        if (len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and not scheduled
+                and all(o.device.type == "cuda" for o in opts)):
             P = opts[0].P
             assert all(o.P is P for o in opts)
             # one norm launch per clipping optimizer, then the one grouped apply reads each one's scale
@@ -337,7 +399,9 @@ class Optimizer:
                 [o.s1 for o in opts], [o.s2 for o in opts], [h for o in opts for h in o._hyper()],
                 [o.beta_pow for o in opts], [o.global_step for o in opts], list(gs_incs), [o.done for o in opts],
                 [o._blob for o in opts], [o.nseg for o in opts], [o.nwork for o in opts],
-                clips if any(c is not None for c in clips) else None)
+                clips if any(c is not None for c in clips) else None, None, None,
+                [int(o.nesterov) for o in opts] if any(o.nesterov for o in opts) else None,
+                [int(o.decay) for o in opts] if any(o.decay for o in opts) else None)
             return
         for o, inc in zip(opts, gs_incs):
             o.step(grad=grad, grad16=grad16, gscale=gscale, gs_inc=inc)
@@ -347,21 +411,30 @@ class Optimizer:
         c = self.cfg
         if clip is not None:  # g * (gscale * scale), as the kernel forms it
             gscale = float(gscale) * float(clip[0])
-        lr_t = c.lr
+        lr = c.lr
+        if self.lr_spec is not None:  # the rate of the step this apply starts from, as the kernel reads it
+            lr = float(ops.lr_schedule_value(self.lr_spec, int(self.global_step.item())))
+            self._lr_out[0] = lr
+        lr_t = lr
         if c.kind == "adam":
             b1p, b2p = self.beta_pow.tolist()
-            lr_t = c.lr * math.sqrt(1 - b2p) / (1 - b1p)
+            lr_t = lr * math.sqrt(1 - b2p) / (1 - b1p)
         eps = c.resolved_eps()
-        for name in self.var_list:
+        for name, wd in zip(self.var_list, self.wd):
             s = self.P.spec(name)
             o, n = self.P.offsets[name], s.numel
             v, g = self.P.master[o:o + n], grad[o:o + n] * gscale
+            if wd:  # coupled L2, after the clip scale
+                g = g + wd * v
             if c.kind == "sgd":
-                v -= c.lr * g
+                v -= lr * g
             elif c.kind == "momentum":
                 a = self.s1[o:o + n]
                 a.mul_(c.momentum).add_(g)
-                v -= c.lr * a
+                if self.nesterov:
+                    v -= g * lr + a * c.momentum * lr
+                else:
+                    v -= lr * a
             elif c.kind == "adam":
                 m, v2 = self.s1[o:o + n], self.s2[o:o + n]
                 m.mul_(c.beta1).add_((1 - c.beta1) * g)
@@ -370,7 +443,7 @@ class Optimizer:
             else:
                 ms, mom = self.s1[o:o + n], self.s2[o:o + n]
                 ms.mul_(c.rho).add_((1 - c.rho) * g * g)
-                mom.mul_(c.momentum).add_(c.lr * g / (ms + eps).sqrt())
+                mom.mul_(c.momentum).add_(lr * g / (ms + eps).sqrt())
                 v -= mom
         if c.kind == "adam":
             self.beta_pow[0] *= c.beta1

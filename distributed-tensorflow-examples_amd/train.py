@@ -119,6 +119,44 @@ CNN_CLIP_ERROR = ("--clip_norm: the MNIST CNN's own schedule applies its fc and 
                   "before its first update; pass --bucket_mb to run the CNN on the generic path, which clips")
 
 
+CNN_RECIPE_ERROR = ("%s: the MNIST CNN's own schedule launches its Adam applies itself, with the learning rate as a "
+                    "host argument; pass --bucket_mb to run the CNN on the generic path, which takes a schedule")
+PS_RECIPE_ERROR = ("%s: learning-rate schedules, --weight_decay and --nesterov run in local and all-reduce mode "
+                   "only - in --mode=ps the shards' optimizers own no global_step to evaluate a schedule from")
+
+
+def check_recipe(flags, model, mode=None):
+    """The optimizer-recipe flags against mode and model, before anything is built.  (The MNIST CNN's
+    own schedule is refused where that schedule is chosen, run_allreduce.)"""
+    names = flagmod.recipe_flags(flags)
+    if not names:
+        return
+    if mode == "ps":
+        raise ValueError(PS_RECIPE_ERROR % " ".join(names))
+    if (flags.weight_decay > 0 or flags.nesterov) and getattr(model, "decay_vars", None) is None:
+        raise ValueError("%s: only a model that declares its decaying variables takes these (resnet20: the conv and "
+                         "dense kernels), not %r" % (" ".join(n for n in names if n in ("--weight_decay", "--nesterov")),
+                                                     getattr(model, "name", "")))
+
+
+def apply_recipe(flags, cfg, model, var_list_):
+    """The optimizer-recipe flags into the OptimizerConfig of one var list (validated by the Optimizer)."""
+    cfg.lr_boundaries, cfg.lr_values = tuple(flags.lr_boundaries), tuple(flags.lr_values)
+    cfg.lr_decay_steps, cfg.lr_end, cfg.lr_warmup_steps = flags.lr_decay_steps, flags.lr_end, flags.lr_warmup_steps
+    if getattr(model, "decay_vars", None) is not None:
+        cfg.weight_decay, cfg.nesterov = flags.weight_decay, bool(flags.nesterov)
+        cfg.decay_vars = tuple(n for n in model.decay_vars if n in var_list_)
+
+
+def lr_metrics(opts) -> dict:
+    """The learning rate the step used, read from the device (``lr``; ``lr_<i>`` per scheduled
+    optimizer of several).  A host read: log steps only."""
+    s = [o for o in opts if o.current_lr is not None]
+    if len(s) == 1:
+        return {"lr": float(s[0].current_lr.item())}
+    return {"lr_%d" % i: float(o.current_lr.item()) for i, o in enumerate(s)}
+
+
 def clip_metrics(clips) -> dict:
     """The step's global gradient norms, read from the device: ``global_norm`` for a single optimizer,
     ``global_norm_<i>`` per optimizer of several (the GAN).  A host read: log steps only."""
@@ -447,19 +485,25 @@ def run_worker_ps(flags, model, server, device, log):
 
 # --------------------------------------------------------------- allreduce
 def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=None):
+    check_recipe(flags, model)
+    recipe = flagmod.recipe_flags(flags)
     prog = model.program(device, flags.batch_size, seed=flags.seed)
     # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
     # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
     # with --clip_norm, which that schedule cannot do)
     native = (hasattr(prog, "attach_data_parallel") and len(model.opt_groups) == 1
-              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0)))
+              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe)))
     if native and flags.clip_norm > 0:
         raise ValueError(CNN_CLIP_ERROR)
+    if native and recipe:
+        raise ValueError(CNN_RECIPE_ERROR % " ".join(recipe))
     gstep = torch.zeros(1, dtype=torch.int32, device=device)
     opts = []
     for i, (cfg, var_list_, bp) in enumerate(model.opt_groups):
         cfg.lr = flags.learning_rate if flags.learning_rate is not None else cfg.lr
         cfg.clip_norm = flags.clip_norm
+        if recipe:
+            apply_recipe(flags, cfg, model, var_list_)
         opts.append(Optimizer(cfg, prog.P, var_list=var_list_, global_step=gstep, beta_power_names=bp))
     is_chief = rank == 0
     sv = Supervisor(
@@ -556,6 +600,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
             sc = scalar_metrics(state.get("m"))
             if clips and local_step % flags.log_every == 0:
                 sc.update(clip_metrics(clips))  # (the all-reduce has completed before step_all: every rank's norm)
+            if recipe and local_step % flags.log_every == 0:
+                sc.update(lr_metrics(opts))
             if local_step == 0 and native and ar is not None and is_chief:
                 log("schedule: " + " < ".join(prog.core.schedule))
             if local_step % flags.log_every == 0:
@@ -656,6 +702,7 @@ def run(model_name: str, argv=None, log=_print):
     torch.manual_seed(flags.seed)
     np.random.seed(flags.seed)
     mode = flagmod.resolve_mode(flags)  # (+ mode-dependent defaults: --heartbeat_secs)
+    check_recipe(flags, model, mode)
     local_rank = int(os.environ.get("LOCAL_RANK", flags.task_index if flags.job_name == "worker" else 0))
     device = resolve_device(flags.device, local_rank)
     if device.type == "cuda":

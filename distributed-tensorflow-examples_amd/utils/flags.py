@@ -21,6 +21,20 @@ def _bool(v):
     return str(v).lower() in ("1", "true", "yes", "y", "t")
 
 
+def _int_list(v):
+    return tuple(int(x) for x in str(v).split(",") if x.strip())
+
+
+def _float_list(v):
+    return tuple(float(x) for x in str(v).split(",") if x.strip())
+
+
+def recipe_flags(flags) -> list:
+    """The optimizer-recipe flags (learning-rate schedule, weight decay, Nesterov) that are set, by name."""
+    names = ("lr_boundaries", "lr_values", "lr_decay_steps", "lr_warmup_steps", "weight_decay", "nesterov")
+    return ["--" + n for n in names if getattr(flags, n, None)]
+
+
 def add_bool(ap, name, default, help_):
     ap.add_argument("--" + name, dest=name, nargs="?", const=True, default=default, type=_bool, help=help_)
     ap.add_argument("--no" + name, dest=name, action="store_false", help=argparse.SUPPRESS)
@@ -107,6 +121,26 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "in the batch-gather launch on GPUs (resnet20 only; its evaluation standardises too); "
                          "none (default): pixels / 255 as they are.  The crop / flip draws are a counter-based "
                          "stream seeded with the worker's data seed; a restart begins its counter at 0 again")
+    ap.add_argument("--lr_boundaries", type=_int_list, default=(),
+                    help="learning-rate schedule, evaluated from global_step inside the fused apply (local / "
+                         "all-reduce modes; the MNIST CNN's own schedule needs --bucket_mb): the steps of "
+                         "tf.train.piecewise_constant, e.g. 32000,48000 (at most 8), with --lr_values")
+    ap.add_argument("--lr_values", type=_float_list, default=(),
+                    help="the rates of --lr_boundaries, one more than boundaries, e.g. 0.1,0.01,0.001: the first "
+                         "while step <= the first boundary, the last beyond the last boundary")
+    ap.add_argument("--lr_decay_steps", type=int, default=0,
+                    help="linear decay (tf.train.polynomial_decay, power 1, no cycling) from --learning_rate to "
+                         "--lr_end over this many steps, constant after; not together with --lr_boundaries")
+    ap.add_argument("--lr_end", type=float, default=0.0, help="the rate --lr_decay_steps ends at")
+    ap.add_argument("--lr_warmup_steps", type=int, default=0,
+                    help="linear warm-up: the rate times (step + 1) / W during the first W steps")
+    ap.add_argument("--weight_decay", type=float, default=0.0,
+                    help="coupled L2 weight decay: D * w is added to the gradient of every variable the model "
+                         "declares as decaying (resnet20: the conv and dense kernels; not batch-norm scales, "
+                         "offsets or biases), after --clip_norm's scale, inside the fused apply.  The logged loss "
+                         "stays the cross-entropy alone, without the L2 term.  0 (default): off")
+    add_bool(ap, "nesterov", False, "Nesterov momentum (TF1 MomentumOptimizer use_nesterov) for models that declare "
+                                    "decaying variables (resnet20)")
     ap.add_argument("--metrics_jsonl", default="", help="append {step, gs, ms, images/sec, loss} lines here")
     ap.add_argument("--heartbeat_secs", type=float, default=None,
                     help="publish a TCPStore heartbeat every N s; 0: off.  Default: %s s in --mode=allreduce "
@@ -130,4 +164,8 @@ def parse(argv=None, model_defaults=None, prog=None):
         ap.error("unknown flags: %s" % " ".join(unknown))
     if not args.clip_norm >= 0:
         ap.error("--clip_norm must be >= 0 (0 = off), got %r" % args.clip_norm)
+    if not args.weight_decay >= 0:
+        ap.error("--weight_decay must be >= 0 (0 = off), got %r" % args.weight_decay)
+    if args.lr_end and not args.lr_decay_steps:
+        ap.error("--lr_end is the end of a linear decay: it needs --lr_decay_steps")
     return args
