@@ -886,9 +886,12 @@ void seq_stage(const Tensor& x, const Tensor& xh, int64_t T, int64_t I, const Te
 
 void gather_rows(const Tensor& src, const Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& labels_src,
                  const optional<Tensor>& labels_dst, int64_t seed, const optional<Tensor>& counter,
-                 const optional<Tensor>& done, at::TensorList zero, const optional<Tensor>& onehot) {
+                 const optional<Tensor>& done, at::TensorList zero, const optional<Tensor>& onehot, bool shuffle) {
   check_cuda(src, "src");
+  TORCH_CHECK(!shuffle || !(idx.has_value() && idx->defined()), "gather_rows: shuffle samples the rows itself, it takes no idx");
+  TORCH_CHECK(!shuffle || (src.size(0) >= 1 && src.size(0) <= (int64_t(1) << 31)), "gather_rows: shuffle needs 1 <= n_rows <= 2^31");
   dtfe::GatherArgs a{};
+  a.sample = shuffle ? dtfe::SAMPLE_SHUFFLE : dtfe::SAMPLE_REPLACE;
   if (onehot.has_value()) {
     check_cuda(*onehot, "onehot");
     TORCH_CHECK(onehot->scalar_type() == at::kFloat && onehot->is_contiguous() && onehot->dim() == 2 &&
@@ -919,7 +922,7 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
                   const optional<Tensor>& mean, const optional<Tensor>& inv_std, const optional<Tensor>& idx,
                   const optional<Tensor>& labels_src, const optional<Tensor>& labels_dst, int64_t seed,
                   const optional<Tensor>& counter, const optional<Tensor>& done, at::TensorList zero,
-                  const optional<Tensor>& onehot) {
+                  const optional<Tensor>& onehot, bool shuffle) {
   auto i32 = [](const optional<Tensor>& t, const char* name, int64_t min_numel) {
     if (!t.has_value() || !t->defined()) return;
     check_cuda(*t, name);
@@ -955,6 +958,8 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
   }
   const int64_t B = dst.size(0);
   i32(idx, "idx", B);
+  TORCH_CHECK(!shuffle || !given(idx), "augment_rows: shuffle samples the rows itself, it takes no idx");
+  a.sample = shuffle ? dtfe::SAMPLE_SHUFFLE : dtfe::SAMPLE_REPLACE;
   i32(labels_src, "labels_src", src.size(0));
   i32(labels_dst, "labels_dst", B);
   TORCH_CHECK(!given(labels_dst) || given(labels_src), "augment_rows: labels_dst needs labels_src");
@@ -1546,11 +1551,11 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("seq_stage(Tensor x, Tensor(a!) xh, int T, int I, Tensor ysrc, Tensor(b!) ydst, Tensor(c!)[] zero) -> ()");
   m.def(
       "gather_rows(Tensor src, Tensor(a!) dst, Tensor? idx, Tensor? labels_src, Tensor(b!)? labels_dst, int seed,"
-      " Tensor(c!)? counter, Tensor(d!)? done, Tensor(e!)[] zero, Tensor(f!)? onehot=None) -> ()");
+      " Tensor(c!)? counter, Tensor(d!)? done, Tensor(e!)[] zero, Tensor(f!)? onehot=None, bool shuffle=False) -> ()");
   m.def(
       "augment_rows(Tensor src, Tensor(a!) dst, int H, int W, int C, int pad, bool flip, Tensor? mean, Tensor? inv_std,"
       " Tensor? idx, Tensor? labels_src, Tensor(b!)? labels_dst, int seed, Tensor(c!)? counter, Tensor(d!)? done,"
-      " Tensor(e!)[] zero, Tensor(f!)? onehot=None) -> ()");
+      " Tensor(e!)[] zero, Tensor(f!)? onehot=None, bool shuffle=False) -> ()");
   m.def("uniform_fill(Tensor(a!) out, float lo, float hi, int seed, Tensor(b!)? counter, Tensor(c!)? done,"
         " Tensor? copy_src=None, Tensor(d!)? copy_dst=None) -> ()");
   m.def("cast_(Tensor src, Tensor(a!) dst) -> ()");

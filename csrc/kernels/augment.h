@@ -1,5 +1,5 @@
 #pragma once
-#include "common.h"
+#include "elementwise.h"
 
 namespace dtfe {
 
@@ -29,6 +29,7 @@ struct AugmentArgs {
   uint64_t seed; int64_t* counter; uint32_t* done;
   uint32_t* zptr[4]; long zlen[4]; int nz;
   float* onehot; int ncls;
+  int sample;  // SampleMode (elementwise.h) of the rows when idx is null; the crop / flip draws are the same in both
 };
 void launch_augment_rows(const AugmentArgs& a, hipStream_t s);
 

@@ -26,10 +26,14 @@ struct Draw { long r; int dy, dx; bool flipped; };
 // Row: the stream of gather_rows.  Crop offsets and flip: one draw of the salted stream per sample.
 // h is uniform over 2^32 values and span^2 * 2 <= 1922, so for pad <= 15 the probability of every
 // dx, dy and flip value is within 2^-22 of uniform (the modulo bias).
-__device__ __forceinline__ Draw aug_draw(const AugmentArgs& a, int b, int64_t step) {
+// SHUF (idx null, SAMPLE_SHUFFLE): the row comes from the epoch permutation; `row` >= 0 hands in one
+// that was resolved already.
+template <bool SHUF>
+__device__ __forceinline__ Draw aug_draw(const AugmentArgs& a, int b, int64_t step, long row = -1) {
   const uint64_t i = (uint64_t)step * a.B + b;
   Draw w;
-  w.r = a.idx ? (long)a.idx[b] : (long)(hash_u32(a.seed, i) % (uint32_t)a.n_rows);
+  if (SHUF) w.r = row >= 0 ? row : shuffled_row(a.seed, step, a.B, a.n_rows, b);
+  else w.r = a.idx ? (long)a.idx[b] : (long)(hash_u32(a.seed, i) % (uint32_t)a.n_rows);
   const uint32_t span = 2u * a.pad + 1u;
   const uint32_t h = hash_u32(a.seed ^ AUG_SALT, i);
   w.dx = (int)(h % span);
@@ -54,15 +58,17 @@ __device__ __forceinline__ void aug_advance_counter(int64_t* counter, uint32_t* 
   }
 }
 
-// one-hot label rows, zero ranges, counter ticket: the tail both kernels share (grid-strided)
+// one-hot label rows, zero ranges, counter ticket: the tail both kernels share (grid-strided).
+// SHUF: the kernels wrote the one-hot rows where they had the sample's row at hand.
+template <bool SHUF>
 __device__ __forceinline__ void aug_tail(const AugmentArgs& a, int64_t step) {
   const long tid = (long)blockIdx.x * AUG_THREADS + threadIdx.x, nth = (long)gridDim.x * AUG_THREADS;
-  if (a.onehot) {
+  if (a.onehot && !SHUF) {
     const long n = (long)a.B * a.ncls;
     for (long i = tid; i < n; i += nth) {
       const int b = (int)(i / a.ncls);
       const int c = (int)(i - (long)b * a.ncls);
-      a.onehot[i] = a.labels_src[aug_draw(a, b, step).r] == c ? 1.f : 0.f;
+      a.onehot[i] = a.labels_src[aug_draw<false>(a, b, step).r] == c ? 1.f : 0.f;
     }
   }
   for (int z = 0; z < a.nz; ++z)
@@ -71,10 +77,11 @@ __device__ __forceinline__ void aug_tail(const AugmentArgs& a, int64_t step) {
 }
 
 // D % 8 == 0, one image <= AUG_LDS_BYTES, C <= AUG_LDS_MAX_C, src / dst 16-byte aligned
-template <bool U8, bool BF>
+template <bool U8, bool BF, bool SHUF>
 __global__ __launch_bounds__(AUG_THREADS) void augment_rows_lds_kernel(AugmentArgs a) {
   __shared__ u32x4_t img4[AUG_LDS_BYTES / 16];
   __shared__ float stat[2 * AUG_LDS_MAX_C];
+  __shared__ int row_s;  // SHUF: the image's source row, resolved by thread 0
   uint8_t* img = reinterpret_cast<uint8_t*>(img4);
   const int64_t step = a.counter ? *a.counter : 0;
   const int D = a.H * a.W * a.C;
@@ -85,8 +92,16 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_rows_lds_kernel(AugmentAr
     stat[AUG_LDS_MAX_C + threadIdx.x] = a.inv_std[threadIdx.x];
   }
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-    const Draw w = aug_draw(a, b, step);
+    if (SHUF) {  // once per image: thread 0 walks the permutation, the workgroup reads the row from LDS
+      if (threadIdx.x == 0) row_s = (int)shuffled_row(a.seed, step, a.B, a.n_rows, b);
+      __syncthreads();  // (the barrier that ends the previous image keeps its readers ahead of this store)
+    }
+    const Draw w = aug_draw<SHUF>(a, b, step, SHUF ? (long)row_s : -1);
     if (a.labels_dst && threadIdx.x == 0) a.labels_dst[b] = a.labels_src[w.r];
+    if (SHUF && a.onehot) {
+      const int lab = a.labels_src[w.r];
+      for (int c = threadIdx.x; c < a.ncls; c += AUG_THREADS) a.onehot[(long)b * a.ncls + c] = lab == c ? 1.f : 0.f;
+    }
     const uint8_t* row = reinterpret_cast<const uint8_t*>(a.src) + w.r * (long)nbytes;
     if ((nbytes & 15) == 0) {
       for (int i = threadIdx.x * 16; i < nbytes; i += AUG_THREADS * 16)
@@ -131,19 +146,38 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_rows_lds_kernel(AugmentAr
     }
     __syncthreads();  // the next image's staging overwrites img
   }
-  aug_tail(a, step);
+  aug_tail<SHUF>(a, step);
 }
 
 // any shape (224x224x3, odd D): one thread per output element, correct rather than fast
+// SHUF: the rows [b0, b0 + cnt) of the workgroup's next AUG_THREADS elements are resolved once, one per
+// thread, into LDS (gather_rows' window); the element with d == 0 writes its sample's one-hot row.
+template <bool SHUF>
 __global__ __launch_bounds__(AUG_THREADS) void augment_rows_elem_kernel(AugmentArgs a) {
+  __shared__ int rows[SHUF ? AUG_THREADS : 1];
   const int64_t step = a.counter ? *a.counter : 0;
   const long D = (long)a.H * a.W * a.C;
   const long n = (long)a.B * D;
-  for (long i = (long)blockIdx.x * AUG_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * AUG_THREADS) {
+  for (long base = (long)blockIdx.x * AUG_THREADS; base < n; base += (long)gridDim.x * AUG_THREADS) {
+    const long i = base + threadIdx.x;
+    int b0 = 0;
+    if (SHUF) {  // (base is uniform: every thread meets the barriers)
+      const long last = base + AUG_THREADS - 1 < n - 1 ? base + AUG_THREADS - 1 : n - 1;
+      b0 = (int)(base / D);
+      const int cnt = (int)(last / D) - b0 + 1;
+      __syncthreads();
+      if ((int)threadIdx.x < cnt) rows[threadIdx.x] = (int)shuffled_row(a.seed, step, a.B, a.n_rows, b0 + (int)threadIdx.x);
+      __syncthreads();
+    }
+    if (i >= n) continue;
     const int b = (int)(i / D);
     const int d = (int)(i - (long)b * D);
-    const Draw w = aug_draw(a, b, step);
+    const Draw w = aug_draw<SHUF>(a, b, step, SHUF ? (long)rows[b - b0] : -1);
     if (a.labels_dst && d == 0) a.labels_dst[b] = a.labels_src[w.r];
+    if (SHUF && a.onehot && d == 0) {
+      const int lab = a.labels_src[w.r];
+      for (int c = 0; c < a.ncls; ++c) a.onehot[(long)b * a.ncls + c] = lab == c ? 1.f : 0.f;
+    }
     const int p = d / a.C, c = d - p * a.C;
     const int y = p / a.W, x = p - y * a.W;
     const int ys = y + w.dy - a.pad;
@@ -158,7 +192,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_rows_elem_kernel(AugmentA
     if (a.dst_dtype == 1) reinterpret_cast<float*>(a.dst)[i] = t;
     else reinterpret_cast<bf16*>(a.dst)[i] = f2bf(t);
   }
-  aug_tail(a, step);
+  aug_tail<SHUF>(a, step);
 }
 
 }  // namespace
@@ -166,25 +200,33 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_rows_elem_kernel(AugmentA
 void launch_augment_rows(const AugmentArgs& a, hipStream_t s) {
   const long D = (long)a.H * a.W * a.C;
   const long esz = a.src_dtype == 0 ? 1 : 4;
+  const bool shuf = !a.idx && a.sample == SAMPLE_SHUFFLE;
   const bool lds = D % 8 == 0 && D * esz <= AUG_LDS_BYTES && a.C <= AUG_LDS_MAX_C &&
                    ((uintptr_t)a.src & 15) == 0 && ((uintptr_t)a.dst & 15) == 0;
   if (lds) {
     long blocks = a.B < 1 ? 1 : a.B;
     if (blocks > 2048) blocks = 2048;
     const dim3 g((unsigned)blocks), t(AUG_THREADS);
+#define AUG_LDS_LAUNCH(U8, BF)                                                                          \
+  do {                                                                                                  \
+    if (shuf) hipLaunchKernelGGL((augment_rows_lds_kernel<U8, BF, true>), g, t, 0, s, a);               \
+    else hipLaunchKernelGGL((augment_rows_lds_kernel<U8, BF, false>), g, t, 0, s, a);                   \
+  } while (0)
     if (a.src_dtype == 0) {
-      if (a.dst_dtype == 2) hipLaunchKernelGGL((augment_rows_lds_kernel<true, true>), g, t, 0, s, a);
-      else hipLaunchKernelGGL((augment_rows_lds_kernel<true, false>), g, t, 0, s, a);
+      if (a.dst_dtype == 2) AUG_LDS_LAUNCH(true, true);
+      else AUG_LDS_LAUNCH(true, false);
     } else {
-      if (a.dst_dtype == 2) hipLaunchKernelGGL((augment_rows_lds_kernel<false, true>), g, t, 0, s, a);
-      else hipLaunchKernelGGL((augment_rows_lds_kernel<false, false>), g, t, 0, s, a);
+      if (a.dst_dtype == 2) AUG_LDS_LAUNCH(false, true);
+      else AUG_LDS_LAUNCH(false, false);
     }
+#undef AUG_LDS_LAUNCH
     return;
   }
   long blocks = ((long)a.B * D + AUG_THREADS - 1) / AUG_THREADS;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(augment_rows_elem_kernel, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, s, a);
+  if (shuf) hipLaunchKernelGGL(augment_rows_elem_kernel<true>, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, s, a);
+  else hipLaunchKernelGGL(augment_rows_elem_kernel<false>, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, s, a);
 }
 
 }  // namespace dtfe

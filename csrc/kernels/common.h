@@ -92,6 +92,53 @@ __device__ __forceinline__ float hash_uniform(uint64_t seed, uint64_t idx) {
   return (hash_u32(seed, idx) >> 8) * (1.0f / 16777216.0f);  // [0,1)
 }
 
+// Keyed permutation of [0, n), 1 <= n <= 2^31, with O(1) state: a balanced Feistel network over the
+// smallest even-width power-of-two domain that holds n, cycle-walked back into [0, n).
+//   bits = bit length of n - 1, rounded up to even, at least 2;  h = bits / 2;  mask = 2^h - 1
+//   one pass over x:  (L, R) = (x >> h, x & mask);  4 rounds r = 0..3 of
+//                     (L, R) <- (R, L ^ (hash_u32(key, epoch << 18 | r << 16 | R) & mask));  x = L << h | R
+//   perm_index(key, epoch, n, i) = the first value below n in  pass(i), pass(pass(i)), ...
+// (R < 2^16 and r < 4 share no bits with epoch << 18, which wraps modulo 2^64.)  A pass is a bijection
+// of [0, 2^bits), so walking its cycle from i < n returns to [0, n) and the map is a bijection of
+// [0, n) for every (key, epoch); the mean number of passes is 2^bits / n < 4.  Integer operations
+// only.  ops.epoch_permutation is the host mirror.
+__device__ __forceinline__ uint32_t perm_index(uint64_t key, uint64_t epoch, uint32_t n, uint32_t i) {
+  int bits = n > 1u ? 32 - __builtin_clz(n - 1u) : 0;
+  bits = bits < 2 ? 2 : (bits + 1) & ~1;
+  const int h = bits >> 1;
+  const uint32_t mask = (1u << h) - 1u;
+  const uint64_t e = epoch << 18;
+  uint32_t x = i;
+  do {
+    uint32_t L = x >> h, R = x & mask;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+      const uint32_t t = L ^ (hash_u32(key, e | (uint64_t)(r << 16) | R) & mask);
+      L = R;
+      R = t;
+    }
+    x = (L << h) | R;
+  } while (x >= n);
+  return x;
+}
+
+// Epoch-exact batch sampling: batch position p = counter * B + b lies in epoch p / n at index p % n
+// and reads row perm_index(seed ^ SHUF_SALT, p / n, n, p % n).  Every row once per epoch; a batch
+// that straddles an epoch boundary stitches the tail of one epoch to the head of the next, freshly
+// permuted one (B > n spans several).  The salt keeps the row stream apart from the with-replacement
+// stream hash_u32(seed, p) and the crop / flip stream (augment.h).  ops.shuffled_rows is the mirror.
+constexpr uint64_t SHUF_SALT = 0x5EED0FE90C45A1D3ull;
+__device__ __forceinline__ long shuffled_row(uint64_t seed, int64_t counter, int B, long n_rows, int b) {
+  // p = base + b with base = counter * B the same for the whole launch: its 64-bit divide is uniform,
+  // and what is left per sample is a 32-bit one (base % n + b < 2^31 + 2^31)
+  const uint64_t base = (uint64_t)counter * (uint64_t)B;
+  const uint32_t n = (uint32_t)n_rows;
+  const uint64_t q0 = base / n;
+  const uint32_t i = (uint32_t)(base - q0 * n) + (uint32_t)b;
+  const uint32_t q1 = i / n;
+  return (long)perm_index(seed ^ SHUF_SALT, q0 + q1, n, i - q1 * n);
+}
+
 // XCD-aware bijective remap of a flat workgroup id (cdna_hip_programming T1):
 // consecutive logical tiles land on the same XCD so they share that XCD's L2.
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {

@@ -8,6 +8,10 @@ namespace dtfe {
 // dst dtype: 1 = f32, 2 = bf16
 // idx == nullptr: indices sampled on device from (seed, *counter) and the
 // counter advanced by the last workgroup, so a replayed graph draws a new batch.
+// Sampling mode of those indices (idx == nullptr only): SAMPLE_REPLACE, with replacement,
+// row(b) = hash_u32(seed, counter * B + b) % n_rows;  SAMPLE_SHUFFLE, one permutation of the rows per
+// epoch, row(b) = shuffled_row(seed, counter, B, n_rows, b) (common.h).
+enum SampleMode : int { SAMPLE_REPLACE = 0, SAMPLE_SHUFFLE = 1 };
 struct GatherArgs {
   const void* src; int src_dtype; long n_rows; int D;
   void* dst; int dst_dtype; int B;
@@ -19,6 +23,7 @@ struct GatherArgs {
   uint32_t* zptr[4]; long zlen[4]; int nz;
   // optional one-hot label rows [B][ncls] fp32 written in the same launch (softmax-xent input)
   float* onehot; int ncls;
+  int sample;  // SampleMode
 };
 void launch_gather_rows(const GatherArgs& a, hipStream_t s);
 

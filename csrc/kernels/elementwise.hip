@@ -50,36 +50,77 @@ __device__ __forceinline__ long gather_src_row(const GatherArgs& a, int b, int64
   return (long)(hash_u32(a.seed, (uint64_t)step * a.B + b) % (uint32_t)a.n_rows);
 }
 
+// SAMPLE_SHUFFLE: a row costs a 64-bit divide and 4 hashes per walk of the permutation, so the rows
+// [b0, b0 + cnt) that the workgroup's next 256 items touch are resolved once, one per thread, into LDS
+// (cnt <= 256: an item belongs to one row and consecutive items to consecutive rows)
+__device__ __forceinline__ void resolve_rows(const GatherArgs& a, int64_t step, int b0, int cnt, int* rows) {
+  __syncthreads();  // the previous window's readers are done
+  if ((int)threadIdx.x < cnt) rows[threadIdx.x] = (int)shuffled_row(a.seed, step, a.B, a.n_rows, b0 + (int)threadIdx.x);
+  __syncthreads();
+}
+
+// one 8-element item: elements [d, d + 8) of source row r -> batch row b (+ the row's label with d == 0)
+__device__ __forceinline__ void gather_item(const GatherArgs& a, int b, int d, long r) {
+  if (a.labels_dst && d == 0) a.labels_dst[b] = a.labels_src[r];
+  float v[8];
+  load8(a.src, a.src_dtype, r * a.D + d, v);
+  const long o = (long)b * a.D + d;
+  if (a.dst_dtype == 1) {
+    f32x4_t* q = reinterpret_cast<f32x4_t*>(reinterpret_cast<float*>(a.dst) + o);
+    q[0] = f32x4_t{v[0], v[1], v[2], v[3]};
+    q[1] = f32x4_t{v[4], v[5], v[6], v[7]};
+  } else {
+    *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16*>(a.dst) + o) =
+        u32x4_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                pack_bf16x2(v[6], v[7])};
+  }
+}
+
 // D % 8 == 0: the batch is flattened into 8-element items (row b, chunk d) spread over the whole
 // grid, so a few long rows (224x224x3 images) still fill every CU; otherwise one wave per row.
+// SHUF (idx == nullptr and SAMPLE_SHUFFLE) is a kernel of its own: the with-replacement kernel carries
+// neither its LDS window nor its barriers, and keeps its loops.
+template <bool SHUF>
 __global__ __launch_bounds__(256) void gather_rows_kernel(GatherArgs a) {
+  __shared__ int rows[SHUF ? 256 : 1];
   const int64_t step = a.counter ? *a.counter : 0;
   if ((a.D % 8) == 0) {
     const int cpr = a.D / 8;
     const long n = (long)a.B * cpr;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-      const int b = (int)(i / cpr);
-      const int d = (int)(i - (long)b * cpr) * 8;
-      const long r = gather_src_row(a, b, step);
-      if (a.labels_dst && d == 0) a.labels_dst[b] = a.labels_src[r];
-      float v[8];
-      load8(a.src, a.src_dtype, r * a.D + d, v);
-      const long o = (long)b * a.D + d;
-      if (a.dst_dtype == 1) {
-        f32x4_t* q = reinterpret_cast<f32x4_t*>(reinterpret_cast<float*>(a.dst) + o);
-        q[0] = f32x4_t{v[0], v[1], v[2], v[3]};
-        q[1] = f32x4_t{v[4], v[5], v[6], v[7]};
-      } else {
-        *reinterpret_cast<u32x4_t*>(reinterpret_cast<bf16*>(a.dst) + o) =
-            u32x4_t{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
-                    pack_bf16x2(v[6], v[7])};
+    if (!SHUF) {
+      for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int b = (int)(i / cpr);
+        const int d = (int)(i - (long)b * cpr) * 8;
+        gather_item(a, b, d, gather_src_row(a, b, step));
+      }
+    } else {
+      // the loop runs on the workgroup's window base, uniform, so every thread meets the barriers
+      for (long base = (long)blockIdx.x * 256; base < n; base += (long)gridDim.x * 256) {
+        const long i = base + threadIdx.x;
+        const long last = base + 255 < n - 1 ? base + 255 : n - 1;
+        const int b0 = (int)(base / cpr);
+        resolve_rows(a, step, b0, (int)(last / cpr) - b0 + 1, rows);
+        if (i >= n) continue;
+        const int b = (int)(i / cpr);
+        const int j = (int)(i - (long)b * cpr);
+        const long r = rows[b - b0];
+        if (a.onehot && j < a.ncls) {  // the row's items share its one-hot row: no second resolve in the tail
+          const int lab = a.labels_src[r];
+          for (int c = j; c < a.ncls; c += cpr) a.onehot[(long)b * a.ncls + c] = lab == c ? 1.f : 0.f;
+        }
+        gather_item(a, b, j * 8, r);
       }
     }
   } else {
     const int lane = threadIdx.x & 63;
     for (int b = blockIdx.x * 4 + (threadIdx.x >> 6); b < a.B; b += gridDim.x * 4) {
-      const long r = gather_src_row(a, b, step);
+      // (SHUF: once per row - b is uniform over the wave that copies the row)
+      const long r = SHUF ? shuffled_row(a.seed, step, a.B, a.n_rows, b) : gather_src_row(a, b, step);
       if (a.labels_dst && lane == 0) a.labels_dst[b] = a.labels_src[r];
+      if (SHUF && a.onehot && lane < a.ncls) {
+        const int lab = a.labels_src[r];
+        for (int c = lane; c < a.ncls; c += 64) a.onehot[(long)b * a.ncls + c] = lab == c ? 1.f : 0.f;
+      }
       for (int d = lane; d < a.D; d += 64) {
         float v;
         if (a.src_dtype == 0) v = reinterpret_cast<const uint8_t*>(a.src)[r * a.D + d] * (1.f / 255.f);
@@ -90,7 +131,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherArgs a) {
       }
     }
   }
-  if (a.onehot) {
+  if (a.onehot && !SHUF) {
     const long n = (long)a.B * a.ncls;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
       const int b = (int)(i / a.ncls);
@@ -107,7 +148,10 @@ void launch_gather_rows(const GatherArgs& a, hipStream_t s) {
   long blocks = (a.D % 8) == 0 ? ((long)a.B * (a.D / 8) + 255) / 256 : (a.B + 3) / 4;
   if (blocks > 2048) blocks = 2048;  // (its tail of counter tickets overlaps the grid's drain)
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, s, a);
+  if (!a.idx && a.sample == SAMPLE_SHUFFLE)
+    hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
 }
 
 // Optionally also copies ncopy floats (16-B aligned, ncopy % 4 == 0) from csrc to cdst in the same

@@ -137,15 +137,28 @@ class DeviceBatcher:
     rows from the host epoch indices as without it, crop / flip draws from a device counter the
     batcher owns (seeded with the DataSet's seed, starting at 0), standardised pixels and the labels
     (one-hot rows included) written by that launch.  ``out``: its destination instead of ``self.x``,
-    e.g. the program's bf16 input buffer, which then needs no further copy."""
+    e.g. the program's bf16 input buffer, which then needs no further copy.
 
-    def __init__(self, ds: DataSet, device, batch_size: int, one_hot: bool = True, augment=None, out=None):
+    ``sampling``: "host" (default) takes the rows from the DataSet's host ``EpochBatcher`` and copies
+    them to the device per batch.  "device" draws them inside the gather launch, from a per-epoch
+    permutation of the rows evaluated from the batcher's counter alone (``ops.shuffled_rows`` is the
+    mirror): no host indices, no host-to-device copy, one launch per batch that also writes the labels
+    and the one-hot rows and advances the counter - so ``next_batch`` can be captured into a step graph
+    and replayed.  The same counter drives the rows and the crop / flip draws; ``seek(k)`` sets it, so a
+    batcher sought to k draws what one that served k batches draws.  (The two modes visit every row once
+    per epoch in different orders.)  Works on CPU tensors too, through the ops' host mirrors."""
+
+    def __init__(self, ds: DataSet, device, batch_size: int, one_hot: bool = True, augment=None, out=None,
+                 sampling: str = "host"):
         from .. import ops
 
         if out is not None and augment is None:
             raise ValueError("DeviceBatcher: out= is the destination of the augmenting launch, it needs augment=")
+        if sampling not in ("host", "device"):
+            raise ValueError("DeviceBatcher: sampling is 'host' or 'device', not %r" % (sampling,))
         self.augment = augment
         self.out = out
+        self.sampling = sampling
 
         self.ops = ops
         self.ds = ds
@@ -162,21 +175,51 @@ class DeviceBatcher:
             if self.device.type == "cuda" else torch.empty(batch_size, dtype=torch.int32)
         if augment is not None:
             self.aug_stats = augment.stats_on(self.device)
+        if augment is not None or sampling == "device":
             self.aug_seed = ds.seed
             self.aug_ctr = torch.zeros(1, dtype=torch.int64, device=self.device)
             self.aug_done = torch.zeros(1, dtype=torch.int32, device=self.device)
 
+    @property
+    def counter(self):
+        """The device counter (int64 [1]): the number of batches served (or sought past)."""
+        return self.aug_ctr
+
+    def seek(self, step: int):
+        """Continue at batch ``step``: the next batch is the one a batcher that served ``step`` batches
+        draws (device sampling: rows and crop / flip draws are functions of this counter alone)."""
+        if self.sampling != "device":
+            raise ValueError("DeviceBatcher.seek: the host EpochBatcher cannot seek; use sampling='device'")
+        self.aug_ctr.fill_(int(step))
+
+    @property
+    def epochs_completed(self):
+        """Whole epochs served.  Device sampling: counter * B // num_examples (a host read of the counter)."""
+        if self.sampling != "device":
+            return self.ds.epochs_completed
+        return int(self.aug_ctr.item()) * self.B // self.ds.num_examples
+
     def next_batch(self):
-        self._host_idx.copy_(torch.from_numpy(self.ds.next_batch_indices(self.B)))
-        self.idx.copy_(self._host_idx, non_blocking=True)
+        shuffle = self.sampling == "device"
+        if shuffle:
+            idx = None
+        else:
+            self._host_idx.copy_(torch.from_numpy(self.ds.next_batch_indices(self.B)))
+            self.idx.copy_(self._host_idx, non_blocking=True)
+            idx = self.idx
         if self.augment is not None:
             a = self.augment
             x = self.x if self.out is None else self.out
             self.ops.augment_rows(self.images, x, a.H, a.W, a.C, pad=a.pad, flip=a.flip, mean=self.aug_stats[0],
-                                  inv_std=self.aug_stats[1], idx=self.idx, labels_src=self.labels,
+                                  inv_std=self.aug_stats[1], idx=idx, labels_src=self.labels,
                                   labels_dst=self.y_int, seed=self.aug_seed, counter=self.aug_ctr, done=self.aug_done,
-                                  onehot=self.y if self.one_hot else None)
+                                  onehot=self.y if self.one_hot else None, shuffle=shuffle)
             return x, (self.y if self.one_hot else self.y_int)
+        if shuffle:
+            self.ops.gather_rows(self.images, self.x, None, self.labels, self.y_int, seed=self.aug_seed,
+                                 counter=self.aug_ctr, done=self.aug_done, onehot=self.y if self.one_hot else None,
+                                 shuffle=True)
+            return self.x, (self.y if self.one_hot else self.y_int)
         self.ops.gather_rows(self.images, self.x, self.idx, self.labels, self.y_int)
         if self.one_hot:
             self.y.zero_()

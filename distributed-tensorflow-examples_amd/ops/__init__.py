@@ -29,7 +29,7 @@ __all__ = [
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
-    "augment_rows", "augment_draws", "AUG_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
+    "augment_rows", "augment_draws", "AUG_SALT", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -174,6 +174,68 @@ def augment_draws(seed, step, B, pad, flip):
     dy = (h // span) % span
     flipped = ((h // (span * span)) & 1).astype(bool) & bool(flip)
     return dy, dx, flipped
+
+
+SHUF_SALT = 0x5EED0FE90C45A1D3  # csrc/kernels/common.h: the epoch permutations' key is seed ^ SHUF_SALT
+
+
+def _perm_index(key, epoch, n, i):
+    """common.h perm_index on arrays: ``epoch`` and ``i`` broadcast together (uint64), one ``n``."""
+    m64 = 0xFFFFFFFFFFFFFFFF
+    n = int(n)
+    bits = max(2, ((n - 1).bit_length() + 1) & ~1)
+    h = np.uint64(bits // 2)
+    mask = np.uint64((1 << (bits // 2)) - 1)
+    epoch, x = np.broadcast_arrays(np.asarray(epoch, dtype=np.uint64), np.asarray(i, dtype=np.uint64))
+    e = epoch << np.uint64(18)  # (wraps modulo 2^64, as on the device)
+    x = x.copy()
+    walk = np.ones(x.shape, dtype=bool)  # the elements still outside [0, n) - all of them take the first pass
+    while walk.any():
+        L, R, ew = x[walk] >> h, x[walk] & mask, e[walk]
+        for r in range(4):
+            L, R = R, L ^ (hash_u32(key & m64, ew | np.uint64(r << 16) | R).astype(np.uint64) & mask)
+        x[walk] = (L << h) | R
+        walk = x >= np.uint64(n)
+    return x.astype(np.int64)
+
+
+def epoch_permutation(seed, epoch, n):
+    """Host mirror of the device's epoch shuffle (common.h perm_index): the permutation of [0, n),
+    1 <= n <= 2^31, that epoch ``epoch`` of the stream ``seed`` visits, int64 [n], bit-exact.
+
+    A balanced Feistel network over the smallest even-width power-of-two domain holding n, cycle-walked:
+    bits = bit length of n - 1 rounded up to even and at least 2, h = bits / 2, mask = 2^h - 1; one pass
+    splits x into (L, R) = (x >> h, x & mask) and runs 4 rounds r = 0..3 of
+        (L, R) <- (R, L ^ (hash_u32(key, epoch << 18 | r << 16 | R) & mask)),   key = seed ^ SHUF_SALT,
+    giving x' = L << h | R; element i is the first value below n among pass(i), pass(pass(i)), ...
+    (epoch << 18 wraps modulo 2^64)."""
+    n = int(n)
+    if not 1 <= n <= 1 << 31:
+        raise ValueError("epoch_permutation: 1 <= n <= 2^31, got %d" % n)
+    m64 = 0xFFFFFFFFFFFFFFFF
+    return _perm_index((int(seed) & m64) ^ SHUF_SALT, np.uint64(int(epoch) & m64), n, np.arange(n, dtype=np.uint64))
+
+
+def shuffled_rows(seed, counter, B, n):
+    """Host mirror of the epoch-exact batch sampling (gather_rows / augment_rows ``shuffle=True``): the
+    rows of the batch at counter value ``counter``, int64 [B].  Position p = counter * B + b reads
+    epoch_permutation(seed, p // n, n)[p % n]: every row once per epoch, a batch that straddles an epoch
+    boundary stitched from the tail of one epoch and the head of the next (B > n spans several)."""
+    n = int(n)
+    if not 1 <= n <= 1 << 31:
+        raise ValueError("shuffled_rows: 1 <= n <= 2^31, got %d" % n)
+    m64 = 0xFFFFFFFFFFFFFFFF
+    p = np.uint64((int(counter) * int(B)) & m64) + np.arange(int(B), dtype=np.uint64)
+    e = p // np.uint64(n)
+    return _perm_index((int(seed) & m64) ^ SHUF_SALT, e, n, p - e * np.uint64(n))
+
+
+def _sampled_rows(seed, counter, B, n, shuffle):
+    """The rows a launch without ``idx`` samples at counter value ``counter`` (torch int64 [B])."""
+    if shuffle:
+        return torch.from_numpy(shuffled_rows(seed, counter, B, n))
+    i = np.uint64((int(counter) * int(B)) & 0xFFFFFFFFFFFFFFFF) + np.arange(int(B), dtype=np.uint64)
+    return torch.from_numpy((hash_u32(seed, i) % np.uint32(n)).astype(np.int64))
 
 
 def _dropout_ref(x, idx, keep, seed, base):
@@ -891,19 +953,28 @@ def seq_stage(x, xh, T, I, y_src, y_dst, zero=()):
 
 
 def gather_rows(src, dst, idx=None, labels_src=None, labels_dst=None, seed=0, counter=None, done=None, zero=(),
-                onehot=None):
+                onehot=None, shuffle=False):
     """dst[b] = src[row(b)] (+ labels); ``zero``: up to 4 contiguous tensors cleared in the same
     launch (a step's accumulators), saving one fill kernel each; ``onehot``: f32 [B][ncls] one-hot
-    rows of the gathered labels, also written in the same launch."""
+    rows of the gathered labels, also written in the same launch.  ``idx`` None samples the rows at
+    counter value s: with replacement, hash_u32(seed, s * B + b) % n_rows, or with ``shuffle=True`` one
+    permutation of the rows per epoch, shuffled_rows(seed, s, B, n_rows)."""
+    if shuffle and idx is not None:
+        raise ValueError("gather_rows: shuffle=True samples the rows itself, it takes no idx")
     if dst.is_cuda:
-        require().gather_rows(src, dst, idx, labels_src, labels_dst, seed, counter, done, list(zero), onehot)
+        require().gather_rows(src, dst, idx, labels_src, labels_dst, seed, counter, done, list(zero), onehot,
+                              bool(shuffle))
         return dst
     for z in zero:
         z.zero_()
+    if idx is None:  # the kernel's on-device sampling, from the host mirror
+        s = int(counter.reshape(-1)[0].item()) if counter is not None else 0
+        idx = _sampled_rows(seed, s, dst.shape[0], src.shape[0], shuffle)
+        if counter is not None and done is not None:  # the kernel's ticket needs both
+            counter += 1
     if onehot is not None:
         onehot.zero_()
         onehot.scatter_(1, labels_src[idx.long()].long().unsqueeze(1), 1.0)
-    assert idx is not None, "CPU gather needs explicit indices"
     rows = src[idx.long()]
     if src.dtype == torch.uint8:
         rows = rows.float() / 255.0
@@ -937,7 +1008,7 @@ def _augment_check(src, dst, H, W, C, pad, mean, inv_std):
 
 
 def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, idx=None, labels_src=None,
-                 labels_dst=None, seed=0, counter=None, done=None, zero=(), onehot=None):
+                 labels_dst=None, seed=0, counter=None, done=None, zero=(), onehot=None, shuffle=False):
     """gather_rows for image rows [n_rows][H*W*C] (uint8 scaled by 1/255, or f32) -> dst [B][H][W][C]
     (f32 / bf16) with the input transforms in the same launch.  Sample b at counter value s draws
     (dy, dx, flipped) = augment_draws(seed, s, B, pad, flip)[b] and
@@ -945,20 +1016,22 @@ def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, 
     with img() = 0 outside the image (the border is zero AFTER standardisation: the mean colour) and
     (v - mean[c]) * inv_std[c] in fp32 inside it (``mean`` None: v).  Rows, labels, one-hot rows, zero
     ranges and the (seed, counter, done) ticket are gather_rows'; ``idx`` None samples the rows
-    hash_u32(seed, s * B + b) % n_rows.  pad = 0, flip off, no statistics: gather_rows bit for bit."""
+    hash_u32(seed, s * B + b) % n_rows, or with ``shuffle=True`` shuffled_rows(seed, s, B, n_rows) (the
+    draws do not depend on the mode).  pad = 0, flip off, no statistics: gather_rows bit for bit."""
     _augment_check(src, dst, H, W, C, pad, mean, inv_std)
+    if shuffle and idx is not None:
+        raise ValueError("augment_rows: shuffle=True samples the rows itself, it takes no idx")
     H, W, C, pad = int(H), int(W), int(C), int(pad)
     if dst.is_cuda:
         require().augment_rows(src, dst, H, W, C, pad, bool(flip), mean, inv_std, idx, labels_src, labels_dst, seed,
-                               counter, done, list(zero), onehot)
+                               counter, done, list(zero), onehot, bool(shuffle))
         return dst
     B = dst.shape[0]
     s = int(counter.reshape(-1)[0].item()) if counter is not None else 0
     if idx is not None:
         rows = idx.reshape(-1)[:B].long()
     else:
-        i = np.uint64((s * B) & 0xFFFFFFFFFFFFFFFF) + np.arange(B, dtype=np.uint64)
-        rows = torch.from_numpy((hash_u32(seed, i) % np.uint32(src.shape[0])).astype(np.int64))
+        rows = _sampled_rows(seed, s, B, src.shape[0], shuffle)
     dy, dx, fl = (torch.from_numpy(a) for a in augment_draws(seed, s, B, pad, flip))
     img = src[rows].reshape(B, H, W, C)
     if src.dtype == torch.uint8:  # the kernel's load: byte * (1.f / 255.f), one fp32 rounding

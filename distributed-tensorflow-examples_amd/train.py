@@ -49,7 +49,7 @@ from .parallel import ps_native
 from .parallel.ps import PSClient, PSServer, Shard, wait_for_init
 from .parallel.supervisor import Supervisor
 from .utils import flags as flagmod
-from .utils.graphs import StepGraph
+from .utils.graphs import MultiStepGraph, StepGraph
 
 MODELS = {
     "gan": (GanModel, GAN_LR),
@@ -108,8 +108,11 @@ def scalar_metrics(metrics) -> dict:
     return out
 
 
-def model_step_hook(model, step, metrics, log):
-    if model.name == "gan" and (step % 1000 == 0 or step == 1):
+def model_step_hook(model, step, metrics, log, ran=1):
+    """``ran``: the steps the iteration ran (a multi-step replay); the line prints when any of their
+    global steps is one it prints at, with the metrics of the last."""
+    inc = getattr(model, "gs_increments", 1)
+    if model.name == "gan" and any(s % 1000 == 0 or s == 1 for s in (step - k * inc for k in range(ran))):
         log("Step %i: Generator Loss: %f, Discriminator Loss: %f"
             % (step, float(metrics["gen_loss"].item()), float(metrics["disc_loss"].item())))
 
@@ -123,6 +126,30 @@ CNN_RECIPE_ERROR = ("%s: the MNIST CNN's own schedule launches its Adam applies 
                     "host argument; pass --bucket_mb to run the CNN on the generic path, which takes a schedule")
 PS_RECIPE_ERROR = ("%s: learning-rate schedules, --weight_decay and --nesterov run in local and all-reduce mode "
                    "only - in --mode=ps the shards' optimizers own no global_step to evaluate a schedule from")
+
+
+SPG_HOST_ERROR = ("--steps_per_graph %d: several steps per replay need --shuffle device - with --shuffle host the rows "
+                  "of every batch are host indices, which cannot enter a replay")
+PS_BATCHING_ERROR = ("%s: device-side shuffling and multi-step replays run in local and all-reduce mode only - a "
+                     "--mode=ps worker's step is paced by its push / pull with the ps tasks")
+CNN_SPG_ERROR = ("--steps_per_graph %d: the MNIST CNN's own schedule is captured one step per replay; pass --bucket_mb "
+                 "to run the CNN on the generic path, which replays several")
+
+
+def batching_flags(flags) -> list:
+    """--shuffle / --steps_per_graph where they differ from their defaults, by name."""
+    return (["--shuffle"] if getattr(flags, "shuffle", "host") != "host" else []) + \
+        (["--steps_per_graph"] if getattr(flags, "steps_per_graph", 1) > 1 else [])
+
+
+def check_batching(flags, mode=None):
+    """--shuffle / --steps_per_graph against mode and each other, before anything is built.  (The MNIST
+    CNN's own schedule is refused where that schedule is chosen, run_allreduce.)"""
+    names = batching_flags(flags)
+    if names and mode == "ps":
+        raise ValueError(PS_BATCHING_ERROR % " ".join(names))
+    if getattr(flags, "steps_per_graph", 1) > 1 and getattr(flags, "shuffle", "host") != "device":
+        raise ValueError(SPG_HOST_ERROR % flags.steps_per_graph)
 
 
 def check_recipe(flags, model, mode=None):
@@ -189,24 +216,40 @@ class Feeder:
     ``augment`` ("none" / "cifar", the --augment flag): the CIFAR input transforms on every training
     batch - on GPUs inside the batcher's one launch, written straight into the program's input buffer;
     on CPU ``ops.augment_rows`` over the host batch.  The draws are seeded with the training set's
-    seed (the per-rank data seed), and ``program.input_norm`` is set so that evaluation standardises too."""
+    seed (the per-rank data seed), and ``program.input_norm`` is set so that evaluation standardises too.
 
-    def __init__(self, data, program, device, augment="none"):
+    ``shuffle`` ("host" / "device", the --shuffle flag): "device" draws the rows of every batch from a
+    per-epoch permutation evaluated inside the batcher's one launch (``DeviceBatcher(sampling="device")``),
+    so ``next()`` can be captured into the step graph; on CPU the same batcher runs on host tensors through
+    the ops' mirrors.  ``seek(k)`` continues at batch k (device mode)."""
+
+    def __init__(self, data, program, device, augment="none", shuffle="host"):
         self.B = program.batch_size
+        self.shuffle = shuffle
         self.dev = None
         self.aug = None
         if augment != "none":
             check_augment(augment, program.model)
             self.aug = cifar.Augment.cifar(data.train.images_u8)
             self.stats = program.input_norm = self.aug.stats_on(device)
-        if device.type == "cuda":
+        if device.type == "cuda" or shuffle == "device":
             self.dev = DeviceBatcher(data.train, device, self.B, one_hot=True, augment=self.aug,
-                                     out=program.x if self.aug is not None else None)
+                                     out=program.x if self.aug is not None and device.type == "cuda" else None,
+                                     sampling=shuffle)
         elif self.aug is not None:
             self.x = torch.empty(self.B, self.aug.H * self.aug.W * self.aug.C)
             self.ctr = torch.zeros(1, dtype=torch.int64)
             self.done = torch.zeros(1, dtype=torch.int32)
         self.data = data
+
+    def seek(self, step: int):
+        """Device mode: the next batch is batch ``step`` of the run (rows and crop / flip draws)."""
+        if self.shuffle == "device":
+            self.dev.seek(step)
+
+    @property
+    def epochs_completed(self):
+        return self.dev.epochs_completed if self.dev is not None else self.data.train.epochs_completed
 
     def next(self):
         if self.dev is not None:
@@ -486,15 +529,20 @@ def run_worker_ps(flags, model, server, device, log):
 # --------------------------------------------------------------- allreduce
 def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=None):
     check_recipe(flags, model)
+    check_batching(flags)
     recipe = flagmod.recipe_flags(flags)
+    spg = max(1, int(getattr(flags, "steps_per_graph", 1)))
+    dev_shuffle = getattr(flags, "shuffle", "host") == "device"
     prog = model.program(device, flags.batch_size, seed=flags.seed)
     # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
     # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
-    # with --clip_norm, which that schedule cannot do)
+    # with --clip_norm, a recipe flag or --steps_per_graph > 1, which that schedule cannot do)
     native = (hasattr(prog, "attach_data_parallel") and len(model.opt_groups) == 1
-              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe)))
+              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe and spg == 1)))
     if native and flags.clip_norm > 0:
         raise ValueError(CNN_CLIP_ERROR)
+    if native and spg > 1:
+        raise ValueError(CNN_SPG_ERROR % spg)
     if native and recipe:
         raise ValueError(CNN_RECIPE_ERROR % " ".join(recipe))
     gstep = torch.zeros(1, dtype=torch.int32, device=device)
@@ -544,7 +592,10 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         prog.attach_data_parallel(ar, opts[0])
     data = read_data_sets(model, "" if flags.synthetic else flags.data_dir, one_hot=True, seed=flags.seed * 1000 + rank + 1,
                           log=log if is_chief else (lambda *_: None))
-    feeder = Feeder(data, prog, device, augment=flags.augment)
+    feeder = Feeder(data, prog, device, augment=flags.augment, shuffle="device" if dev_shuffle else "host")
+    # --shuffle device: rows and crop / flip draws are functions of the batch number, so a restored run
+    # (the chief's state, broadcast above) continues the epoch order and the augmentation stream
+    feeder.seek(int(gstep.item()) // model.gs_increments)
     metrics_log = MetricsLog(flags.metrics_jsonl)
 
     state = {}
@@ -565,6 +616,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
                           interval=min(1.0, flags.heartbeat_secs), timeout=flags.heartbeat_timeout, log=log)
 
     def train_step():
+        if dev_shuffle:  # the batch draw is one launch off the feeder's device counter: part of the captured step
+            prog.load_batch(feeder.next())
         if native:  # forward, backward, overlapped all-reduce and Adam in the program's own order
             with phase("step"):
                 state["m"] = prog.train_step(grad16=ar.grad16 if ar is not None else None, gscale=1.0 / world)
@@ -582,30 +635,53 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
             Optimizer.step_all(opts, [model.gs_increments if i == len(opts) - 1 else 0 for i in range(len(opts))],
                                grad16=g16, gscale=1.0 / world)
 
-    runner = StepGraph(train_step, warmup=2, capture_error_mode="thread_local",
-                       enabled=(device.type == "cuda" and (world == 1 or ar.comm is not None) and flags.hip_graph
-                                and timer is None))
+    # one step per replay, or --steps_per_graph of them (and single-step replays for a remainder)
+    runner = MultiStepGraph(train_step, spg, warmup=2, capture_error_mode="thread_local",
+                            enabled=(device.type == "cuda" and (world == 1 or ar.comm is not None) and flags.hip_graph
+                                     and timer is None))
+    prog.step_runner = runner  # (tests and tools read .graph / .capture_error)
     begin_time = time.time()
     step = int(gstep.item())
     local_step = 0
+    capture_error_logged = graph_logged = False
     try:
         while not sv.should_stop() and step < flags.num_steps:
             t0 = time.time()
-            prog.load_batch(feeder.next())
-            runner()
+            # never past --num_steps: a whole S-step replay only while S steps remain (each advances
+            # global_step by gs_increments), else one step; the graphs capture themselves on the way
+            left = -(-(flags.num_steps - step) // model.gs_increments)
+            if not dev_shuffle:
+                prog.load_batch(feeder.next())
+            if runner.many is not None and left >= spg:
+                runner.many()
+                ran = spg
+            else:
+                runner.one()
+                ran = 1
+            if spg > 1 and not graph_logged and runner.many.graph is not None:
+                graph_logged = True
+                log("hip_graph: captured %d steps per replay" % spg)
+            if runner.capture_error is not None and not capture_error_logged:
+                capture_error_logged = True  # the step runs on, eagerly: say so once
+                log("capture_error: %s: %s; continuing with eager launches"
+                    % (type(runner.capture_error).__name__, runner.capture_error))
             step = int(gstep.item())
             faults.step(step)
-            elapsed = time.time() - t0
+            elapsed = (time.time() - t0) / ran
             ips = prog.batch_size * world / max(elapsed, 1e-9)
             sc = scalar_metrics(state.get("m"))
-            if clips and local_step % flags.log_every == 0:
+            # a log step: a multiple of --log_every lies among the local steps this replay ran
+            log_step = (local_step + ran - 1) // flags.log_every > (local_step - 1) // flags.log_every
+            if clips and log_step:
                 sc.update(clip_metrics(clips))  # (the all-reduce has completed before step_all: every rank's norm)
-            if recipe and local_step % flags.log_every == 0:
+            if recipe and log_step:
                 sc.update(lr_metrics(opts))
             if local_step == 0 and native and ar is not None and is_chief:
                 log("schedule: " + " < ".join(prog.core.schedule))
-            if local_step % flags.log_every == 0:
-                log(step_line(step, local_step, elapsed * 1000, flags.py2_print))
+            if log_step:
+                if dev_shuffle:
+                    sc["epoch"] = feeder.epochs_completed
+                log(step_line(step, local_step + ran - 1, elapsed * 1000, flags.py2_print))
                 if timer is not None:
                     log(PhaseTimer.format(timer.summary()))
                 sv.summary(step, dict(sc, **{"images/sec": ips}))
@@ -613,9 +689,11 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
                     ar.comm.check_health()  # IPC barrier timeouts fail the job on every rank
                 prog.check_health()
             if "m" in state:
-                model_step_hook(model, step, state["m"], log)
-            metrics_log.write(step=local_step, gs=step, ms=elapsed * 1000, images_per_sec=ips, **sc)
-            local_step += 1
+                model_step_hook(model, step, state["m"], log, ran)
+            # one line per replay: the replay's last step, ms = replay time / steps run
+            metrics_log.write(step=local_step + ran - 1, gs=step, ms=elapsed * 1000, images_per_sec=ips,
+                              **(dict(sc, steps=ran) if spg > 1 else sc))
+            local_step += ran
         if wd is not None:  # training is over: peers may now leave at their own pace
             wd.stop()
             _leave_watchdog(store, rank, world, flags.heartbeat_timeout)
@@ -703,6 +781,7 @@ def run(model_name: str, argv=None, log=_print):
     np.random.seed(flags.seed)
     mode = flagmod.resolve_mode(flags)  # (+ mode-dependent defaults: --heartbeat_secs)
     check_recipe(flags, model, mode)
+    check_batching(flags, mode)
     local_rank = int(os.environ.get("LOCAL_RANK", flags.task_index if flags.job_name == "worker" else 0))
     device = resolve_device(flags.device, local_rank)
     if device.type == "cuda":

@@ -120,7 +120,20 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "training set's statistics, 4-pixel zero pad + random 32x32 crop, random horizontal flip, "
                          "in the batch-gather launch on GPUs (resnet20 only; its evaluation standardises too); "
                          "none (default): pixels / 255 as they are.  The crop / flip draws are a counter-based "
-                         "stream seeded with the worker's data seed; a restart begins its counter at 0 again")
+                         "stream seeded with the worker's data seed; a restart begins its counter at 0 again (with "
+                         "--shuffle device: at the restored global step)")
+    ap.add_argument("--shuffle", choices=["host", "device"], default="host",
+                    help="where a batch's rows are chosen (local / all-reduce modes): host = the host EpochBatcher's "
+                         "indices, copied to the device per step (the default); device = a per-epoch permutation of "
+                         "the training set evaluated inside the batch-gather launch from a device counter, so the "
+                         "batch draw is captured with the step.  Both visit every image once per epoch (in different "
+                         "orders); device mode continues the epoch order and the crop / flip stream after a restart, and "
+                         "its log steps report 'epoch' (host mode's metrics lines stay as they were)")
+    ap.add_argument("--steps_per_graph", type=int, default=1,
+                    help="training steps per hipGraph replay (needs --shuffle device: host indices cannot enter a "
+                         "replay).  The loop's unit becomes a replay: stop checks, the metrics line and the step line "
+                         "come once per replay; --num_steps is never overshot (the remainder runs one step per replay); "
+                         "the graphs are captured by the run's first replays, whose ms include the capture")
     ap.add_argument("--lr_boundaries", type=_int_list, default=(),
                     help="learning-rate schedule, evaluated from global_step inside the fused apply (local / "
                          "all-reduce modes; the MNIST CNN's own schedule needs --bucket_mb): the steps of "
@@ -166,6 +179,8 @@ def parse(argv=None, model_defaults=None, prog=None):
         ap.error("--clip_norm must be >= 0 (0 = off), got %r" % args.clip_norm)
     if not args.weight_decay >= 0:
         ap.error("--weight_decay must be >= 0 (0 = off), got %r" % args.weight_decay)
+    if not args.steps_per_graph >= 1:
+        ap.error("--steps_per_graph must be >= 1, got %r" % args.steps_per_graph)
     if args.lr_end and not args.lr_decay_steps:
         ap.error("--lr_end is the end of a linear decay: it needs --lr_decay_steps")
     return args
