@@ -41,6 +41,7 @@
 
 #include "../kernels/optim.h"
 #include "../kernels/ps_link.h"
+#include "opt_state.h"
 
 using at::Tensor;
 
@@ -299,6 +300,7 @@ struct SubPlan {
   int nwork = 0;
 };
 struct Group {
+  c10::intrusive_ptr<OptStateObj> opt;  // owns what args points to
   dtfe::OptArgs args;    // g / g16 and done_counter set per launch
   bool g16;
   std::vector<dtfe::OptSeg> hsegs;   // host copies of the plan (for the bucket sub-plans)
@@ -390,31 +392,28 @@ int64_t ps_service_create(int64_t shm, int64_t nworkers, int64_t device, bool sy
   return (int64_t)g_svc.size() - 1;
 }
 
-void ps_service_add_group(int64_t h, int64_t kind, Tensor p, const c10::optional<Tensor>& s1,
-                          const c10::optional<Tensor>& s2, double lr, double beta1, double beta2, double eps,
-                          double momentum, double rho, const c10::optional<Tensor>& beta_pow,
-                          const c10::optional<Tensor>& global_step, int64_t gs_inc, const Tensor& blob, int64_t nseg,
-                          int64_t nwork, bool g16) {
+void ps_service_add_group(int64_t h, const c10::intrusive_ptr<OptStateObj>& o, double lr,
+                          const c10::optional<Tensor>& global_step, int64_t gs_inc, bool g16) {
   Service* s = svc_of(h);
+  TORCH_CHECK(!o->args.sched && !o->args.nesterov && !o->args.decay,
+              "dtfe ps: the service applies the plain optimizers (no schedule, Nesterov or weight decay)");
   Group g{};
-  auto& a = g.args;
-  a.kind = (int)kind;
-  a.p = p.data_ptr<float>();
-  a.gscale = 1.f;
-  a.s1 = (s1.has_value() && s1->defined()) ? s1->data_ptr<float>() : nullptr;
-  a.s2 = (s2.has_value() && s2->defined()) ? s2->data_ptr<float>() : nullptr;
-  a.lr = (float)lr; a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps;
-  a.momentum = (float)momentum; a.rho = (float)rho;
-  a.beta_pow = (beta_pow.has_value() && beta_pow->defined()) ? beta_pow->data_ptr<float>() : nullptr;
-  a.global_step = (global_step.has_value() && global_step->defined()) ? global_step->data_ptr<int32_t>() : nullptr;
-  a.gs_inc = (int)gs_inc;
-  dtfe::opt_blob_plan(blob.data_ptr(), (size_t)nseg, a);
-  a.nwork = (int)nwork;
+  g.opt = o;
+  g.args = o->args;  // done_counter is set per launch (each worker channel has its own)
+  g.args.done_counter = nullptr;
+  g.args.gscale = 1.f;
+  g.args.lr = (float)lr;
+  g.args.global_step = nullptr;
+  if (global_step.has_value() && global_step->defined()) {
+    TORCH_CHECK(global_step->is_cuda() && global_step->get_device() == o->dev &&
+                    global_step->scalar_type() == at::kInt && global_step->numel() >= 1,
+                "dtfe ps: global_step is an int32 scalar on the optimizer's GPU");
+    g.args.global_step = global_step->data_ptr<int32_t>();
+  }
+  g.args.gs_inc = (int)gs_inc;
   g.g16 = g16;
-  g.hsegs.resize((size_t)nseg);
-  g.hwork.resize((size_t)nwork);
-  if (nseg) hchk(hipMemcpy(g.hsegs.data(), a.segs, (size_t)nseg * sizeof(dtfe::OptSeg), hipMemcpyDeviceToHost), "plan segs D2H");
-  if (nwork) hchk(hipMemcpy(g.hwork.data(), a.work, (size_t)nwork * sizeof(dtfe::OptWork), hipMemcpyDeviceToHost), "plan work D2H");
+  g.hsegs = o->segs;
+  g.hwork = o->work;
   s->groups.push_back(g);
 }
 
@@ -1004,9 +1003,9 @@ TORCH_LIBRARY_FRAGMENT(dtfe, m) {
   m.def("ps_wait(int[] shms, int w, int gs_slot, Tensor ctr, Tensor(a!)? gs_out, Tensor(b!)? ver_out, Tensor(c!) err,"
         " float timeout_s) -> ()", &ps_wait);
   m.def("ps_service_create(int shm, int nworkers, int device, bool sync, int R, bool hogwild) -> int", &ps_service_create);
-  m.def("ps_service_add_group(int h, int kind, Tensor(a!) p, Tensor(b!)? s1, Tensor(c!)? s2, float lr, float beta1,"
-        " float beta2, float eps, float momentum, float rho, Tensor(d!)? beta_pow, Tensor(e!)? global_step, int gs_inc,"
-        " Tensor blob, int nseg, int nwork, bool g16) -> ()", &ps_service_add_group);
+  opt_state_register();
+  m.def("ps_service_add_group(int h, __torch__.torch.classes.dtfe.OptState o, float lr, Tensor? global_step,"
+        " int gs_inc, bool g16) -> ()", &ps_service_add_group);
   m.def("ps_service_set_worker(int h, int w, int mailbox_addr, Tensor snap, int snap_nseg, int snap_nwork) -> ()",
         &ps_service_set_worker);
   m.def("ps_service_set_total(int h, int total) -> ()", &ps_service_set_total);

@@ -8,6 +8,8 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "../kernels/augment.h"
@@ -21,6 +23,7 @@
 #include "../kernels/lstm_seq.h"
 #include "../kernels/gradnorm.h"
 #include "../kernels/optim.h"
+#include "opt_state.h"
 
 using at::Tensor;
 using c10::optional;
@@ -578,78 +581,121 @@ void head_wgrad(const Tensor& dl, const Tensor& h, const Tensor& dw, const optio
   dtfe::launch_head_wgrad(a, cur_stream());
 }
 
+}  // namespace
+
 // -------------------------------------------------------------- optimizer
-// segs: int64 [nseg, 6] = (off, R, T, C, w16_ptr, wt16_ptr)
-// work: int64 [nwork, 7] = (kind, seg, t, r0, c0, start, count)
-// wd:   optional float32 [nseg], the L2 weight decay of each segment (absent: 0 everywhere)
-// returns a device blob holding both struct arrays
-Tensor opt_pack(const Tensor& segs, const Tensor& work, const Tensor& device_like, const optional<Tensor>& wd) {
-  TORCH_CHECK(segs.device().is_cpu() && work.device().is_cpu(), "opt_pack: CPU int64 tables");
-  auto S = segs.contiguous(), Wk = work.contiguous();
-  const int64_t ns = S.size(0), nw = Wk.size(0);
-  std::vector<dtfe::OptSeg> vs(ns);
-  std::vector<dtfe::OptWork> vw(nw);
-  const int64_t* s = S.data_ptr<int64_t>();
-  const int64_t* w = Wk.data_ptr<int64_t>();
+// torch.classes.dtfe.OptState (opt_state.h).  Everything a launch will dereference is checked here, once: the tensors (device, dtype, contiguity,
+// length) and the plan (every segment inside p, every work item inside its segment).
+OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<Tensor> s2, double beta1, double beta2,
+                         double eps, double momentum, double rho, optional<Tensor> beta_pow,
+                         optional<Tensor> global_step, Tensor done, const Tensor& segs_t, const Tensor& work_t,
+                         const optional<Tensor>& wd, optional<Tensor> sched, optional<Tensor> lr_out, bool nesterov,
+                         bool decay) {
+  TORCH_CHECK(kind >= dtfe::OPT_SGD && kind <= dtfe::OPT_RMSPROP, "OptState: kind is 0 (sgd) .. 3 (rmsprop)");
+  check_cuda(p, "p");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous(), "OptState: p is contiguous float32");
+  dev = p.get_device();
+  numel = p.numel();
+  held.push_back(p);
+  // an optional device tensor of the state: null when absent, else checked, held and its address
+  auto bind = [&](const optional<Tensor>& t, const char* name, bool dtype_ok, const char* dtype, int64_t least,
+                  bool exact) -> void* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->get_device() == dev, "OptState: ", name, " is not on p's GPU");
+    TORCH_CHECK(dtype_ok && t->is_contiguous() && (exact ? t->numel() == least : t->numel() >= least), "OptState: ",
+                name, " is contiguous ", dtype, " with ", exact ? "" : "at least ", least, " elements");
+    held.push_back(*t);
+    return t->data_ptr();
+  };
+  auto is = [](const optional<Tensor>& t, at::ScalarType st) {
+    return t.has_value() && t->defined() && t->scalar_type() == st;
+  };
+  auto& a = args;
+  a.kind = (int)kind;
+  a.p = p.data_ptr<float>();
+  a.s1 = (float*)bind(s1, "s1", is(s1, at::kFloat), "float32", numel, true);
+  a.s2 = (float*)bind(s2, "s2", is(s2, at::kFloat), "float32", numel, true);
+  a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps; a.momentum = (float)momentum; a.rho = (float)rho;
+  a.beta_pow = (float*)bind(beta_pow, "beta_pow", is(beta_pow, at::kFloat), "float32", 2, false);
+  a.global_step = (int32_t*)bind(global_step, "global_step", is(global_step, at::kInt), "int32", 1, false);
+  a.done_counter = (uint32_t*)bind(done, "done", done.element_size() == 4, "4-byte", 1, false);
+  if (kind == dtfe::OPT_ADAM) TORCH_CHECK(a.beta_pow && a.s1 && a.s2, "OptState: adam needs slots and beta powers");
+  if (kind == dtfe::OPT_RMSPROP) TORCH_CHECK(a.s1 && a.s2, "OptState: rmsprop needs slots");
+  if (kind == dtfe::OPT_MOMENTUM) TORCH_CHECK(a.s1, "OptState: momentum needs a slot");
+  a.sched = (const dtfe::LrSchedule*)bind(sched, "sched (the blob of lr_schedule_pack)", is(sched, at::kByte), "uint8",
+                                          (int64_t)sizeof(dtfe::LrSchedule), true);
+  TORCH_CHECK(!a.sched || a.global_step, "OptState: a learning-rate schedule needs a global_step");
+  a.lr_out = (float*)bind(lr_out, "lr_out", is(lr_out, at::kFloat), "float32", 1, false);
+  TORCH_CHECK(!nesterov || kind == dtfe::OPT_MOMENTUM, "OptState: nesterov is for the momentum optimizer");
+  a.nesterov = nesterov ? 1 : 0;
+  a.decay = decay ? 1 : 0;
+
+  auto table = [](const Tensor& t, const char* name, int64_t cols) {
+    TORCH_CHECK(t.device().is_cpu() && t.scalar_type() == at::kLong && t.dim() == 2 && t.size(1) == cols, "OptState: ",
+                name, " is a CPU int64 [n, ", cols, "] table");
+    return t.contiguous();
+  };
+  const Tensor S = table(segs_t, "segs", 6), W = table(work_t, "work", 7);
+  const int64_t ns = S.size(0), nw = W.size(0);
+  TORCH_CHECK(nw <= INT32_MAX, "OptState: work has too many items");
   Tensor D;
   if (wd.has_value() && wd->defined()) {
     TORCH_CHECK(wd->device().is_cpu() && wd->scalar_type() == at::kFloat && wd->dim() == 1 && wd->size(0) == ns,
-                "opt_pack: wd is a CPU float32 [nseg] vector");
+                "OptState: wd is a CPU float32 [nseg] vector");
     D = wd->contiguous();
   }
+  segs.resize((size_t)ns);
+  work.resize((size_t)nw);
+  std::vector<int64_t> len((size_t)ns);  // R * T * C of each segment
   for (int64_t i = 0; i < ns; ++i) {
-    vs[i].off = s[i * 6 + 0];
-    vs[i].R = (int)s[i * 6 + 1]; vs[i].T = (int)s[i * 6 + 2]; vs[i].C = (int)s[i * 6 + 3];
-    vs[i].wd = D.defined() ? D.data_ptr<float>()[i] : 0.f;
-    vs[i].w16 = reinterpret_cast<dtfe::bf16*>(s[i * 6 + 4]);
-    vs[i].wt16 = reinterpret_cast<dtfe::bf16*>(s[i * 6 + 5]);
+    const int64_t* s = S.data_ptr<int64_t>() + i * 6;
+    const int64_t off = s[0], R = s[1], T = s[2], C = s[3];
+    // in this order no product overflows: each factor is at most numel before the next multiplies it
+    TORCH_CHECK(off >= 0 && off <= numel && R >= 1 && T >= 1 && C >= 1 && R <= numel && T <= numel / R &&
+                    C <= (numel - off) / (R * T) && std::max({R, T, C}) <= INT32_MAX,
+                "OptState: segs[", i, "] (off ", off, ", R ", R, ", T ", T, ", C ", C, ") does not lie inside p [", numel, "]");
+    const float w = D.defined() ? D.data_ptr<float>()[i] : 0.f;
+    TORCH_CHECK(std::isfinite(w) && w >= 0.f, "OptState: wd[", i, "] is finite and >= 0, got ", w);
+    len[(size_t)i] = R * T * C;
+    auto& g = segs[(size_t)i];
+    g.off = off; g.R = (int)R; g.T = (int)T; g.C = (int)C; g.wd = w;
+    g.w16 = reinterpret_cast<dtfe::bf16*>(s[4]);
+    g.wt16 = reinterpret_cast<dtfe::bf16*>(s[5]);
   }
   for (int64_t i = 0; i < nw; ++i) {
-    vw[i].kind = (int)w[i * 7 + 0]; vw[i].seg = (int)w[i * 7 + 1]; vw[i].t = (int)w[i * 7 + 2];
-    vw[i].r0 = (int)w[i * 7 + 3]; vw[i].c0 = (int)w[i * 7 + 4];
-    vw[i].start = w[i * 7 + 5]; vw[i].count = w[i * 7 + 6];
+    const int64_t* w = W.data_ptr<int64_t>() + i * 7;
+    const int64_t k = w[0], sg = w[1], t = w[2], r0 = w[3], c0 = w[4], start = w[5], count = w[6];
+    TORCH_CHECK((k == 0 || k == 1) && sg >= 0 && sg < ns, "OptState: work[", i, "] has kind ", k, " (0 flat, 1 tile) and"
+                " segment ", sg, " of ", ns);
+    const auto& g = segs[(size_t)sg];
+    if (k == 0) {
+      TORCH_CHECK(start >= 0 && count >= 0 && start <= len[(size_t)sg] && count <= len[(size_t)sg] - start,
+                  "OptState: work[", i, "] flat range (start ", start, ", count ", count, ") runs past segment ", sg,
+                  " [", len[(size_t)sg], "]");
+    } else {
+      TORCH_CHECK(t >= 0 && t < g.T && r0 >= 0 && r0 < g.R && c0 >= 0 && c0 < g.C && g.wt16, "OptState: work[", i,
+                  "] tile (t ", t, ", r0 ", r0, ", c0 ", c0, ") needs a segment with a wt16 copy and t < T, r0 < R, c0 < C");
+    }
+    work[(size_t)i] = dtfe::OptWork{(int)k, (int)sg, (int)t, (int)r0, (int)c0, start, count};
   }
-  const size_t bs = ns * sizeof(dtfe::OptSeg), bw = nw * sizeof(dtfe::OptWork);
-  const size_t off_w = dtfe::opt_blob_work_offset(ns);
+  // the device blob: both struct arrays (optim.h opt_blob_work_offset)
+  const size_t bs = ns * sizeof(dtfe::OptSeg), bw = nw * sizeof(dtfe::OptWork), off_w = dtfe::opt_blob_work_offset(ns);
   Tensor host = at::empty({(int64_t)(off_w + bw)}, at::TensorOptions().dtype(at::kByte));
-  std::memcpy(host.data_ptr(), vs.data(), bs);
-  std::memcpy((char*)host.data_ptr() + off_w, vw.data(), bw);
-  return host.to(device_like.device());
+  if (bs) std::memcpy(host.data_ptr(), segs.data(), bs);
+  if (bw) std::memcpy((char*)host.data_ptr() + off_w, work.data(), bw);
+  held.push_back(host.to(p.device()));
+  dtfe::opt_blob_plan(held.back().data_ptr(), (size_t)ns, a);
+  a.nwork = (int)nw;
 }
+
+namespace {
+
+using OptStateArg = c10::intrusive_ptr<OptStateObj>;
 
 void epoch_signal(const Tensor& ctr) {
   check_cuda(ctr, "ctr");
   TORCH_CHECK(ctr.scalar_type() == at::kInt && ctr.numel() >= 1, "epoch_signal: int32 counter");
   dtfe::launch_epoch_signal(ctr.data_ptr<int>(), cur_stream());
-}
-
-// the launch arguments of one optimizer (hyper: lr, beta1, beta2, eps, momentum, rho), shared by the
-// single and the grouped op
-dtfe::OptArgs opt_args(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
-                       double gscale, const optional<Tensor>& s1, const optional<Tensor>& s2, const double* hyper,
-                       const optional<Tensor>& beta_pow, const optional<Tensor>& global_step, int64_t gs_inc,
-                       const Tensor& done, const Tensor& blob, int64_t nseg, int64_t nwork) {
-  check_cuda(p, "p");
-  dtfe::OptArgs a{};
-  a.kind = (int)kind;
-  a.p = p.data_ptr<float>();
-  a.g = ptr_or_null<float>(g);
-  a.g16 = ptr_or_null<dtfe::bf16>(g16);
-  TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "apply_gradients: exactly one of g / g16");
-  a.gscale = (float)gscale;
-  a.s1 = ptr_or_null<float>(s1); a.s2 = ptr_or_null<float>(s2);
-  a.lr = (float)hyper[0]; a.beta1 = (float)hyper[1]; a.beta2 = (float)hyper[2]; a.eps = (float)hyper[3];
-  a.momentum = (float)hyper[4]; a.rho = (float)hyper[5];
-  a.beta_pow = ptr_or_null<float>(beta_pow);
-  a.global_step = ptr_or_null<int32_t>(global_step);
-  a.gs_inc = (int)gs_inc;
-  a.done_counter = reinterpret_cast<uint32_t*>(done.data_ptr());
-  dtfe::opt_blob_plan(blob.data_ptr(), (size_t)nseg, a);
-  a.nwork = (int)nwork;
-  if (kind == dtfe::OPT_ADAM) TORCH_CHECK(a.beta_pow && a.s1 && a.s2, "adam needs slots and beta powers");
-  if (kind == dtfe::OPT_RMSPROP) TORCH_CHECK(a.s1 && a.s2, "rmsprop needs slots");
-  if (kind == dtfe::OPT_MOMENTUM) TORCH_CHECK(a.s1, "momentum needs a slot");
-  return a;
 }
 
 // the device scalar of a global-norm clip (grad_sumsq's out[1:]) multiplied into gscale; null when not given
@@ -737,39 +783,34 @@ Tensor lr_schedule_pack(int64_t kind, at::IntArrayRef bounds, at::ArrayRef<doubl
   return host.to(device_like.device());
 }
 
-// the trailing optional arguments of both apply ops: schedule blob, rate output, flags
-void opt_extras(dtfe::OptArgs& a, const optional<Tensor>& sched, const optional<Tensor>& lr_out, bool nesterov, bool decay) {
-  if (sched.has_value() && sched->defined()) {
-    check_cuda(*sched, "sched");
-    TORCH_CHECK(sched->scalar_type() == at::kByte && sched->is_contiguous() &&
-                    sched->numel() == (int64_t)sizeof(dtfe::LrSchedule),
-                "apply_gradients: sched is the blob of lr_schedule_pack");
-    TORCH_CHECK(a.global_step, "apply_gradients: a learning-rate schedule needs a global_step");
-    a.sched = reinterpret_cast<const dtfe::LrSchedule*>(sched->data_ptr());
-  }
-  if (lr_out.has_value() && lr_out->defined()) {
-    check_cuda(*lr_out, "lr_out");
-    TORCH_CHECK(lr_out->scalar_type() == at::kFloat && lr_out->numel() >= 1, "apply_gradients: lr_out is a float32 scalar");
-    a.lr_out = lr_out->data_ptr<float>();
-  }
-  TORCH_CHECK(!nesterov || a.kind == dtfe::OPT_MOMENTUM, "apply_gradients: nesterov is for the momentum optimizer");
-  a.nesterov = nesterov ? 1 : 0;
-  a.decay = decay ? 1 : 0;
+// one launch of a bound optimizer: its template plus what varies, the gradient checked against it
+dtfe::OptArgs opt_launch_args(const OptStateObj& o, const optional<Tensor>& g, const optional<Tensor>& g16,
+                              double gscale, double lr, int64_t gs_inc, const optional<Tensor>& clip_scale) {
+  const bool f32 = g.has_value() && g->defined();
+  TORCH_CHECK(f32 != (g16.has_value() && g16->defined()), "apply_gradients: exactly one of g / g16");
+  const Tensor& t = f32 ? *g : *g16;
+  const char* name = f32 ? "g" : "g16";
+  TORCH_CHECK(t.is_cuda() && t.get_device() == o.dev, "apply_gradients: ", name, " is not on the optimizer's GPU");
+  TORCH_CHECK(t.scalar_type() == (f32 ? at::kFloat : at::kBFloat16) && t.is_contiguous() && t.numel() >= o.numel,
+              "apply_gradients: ", name, " is contiguous ", f32 ? "float32" : "bfloat16", " with at least ", o.numel,
+              " elements (p's)");
+  dtfe::OptArgs a = o.args;
+  if (f32) a.g = t.data_ptr<float>();
+  else a.g16 = reinterpret_cast<const dtfe::bf16*>(t.data_ptr());
+  a.gscale = (float)gscale;
+  a.lr = (float)lr;
+  a.gs_inc = (int)gs_inc;
+  a.clip_scale = clip_scale_ptr(clip_scale);
+  return a;
 }
 
 // wait_done / wait_seen / wait_segs: this launch's items of the segments in the bit mask wait on the
 // device-side counter pair (OptArgs::wait_done / wait_seen) - a gradient produced on another stream with
 // no graph edge to the optimizer launch (the CNN's conv2 weight-gradient branch)
-void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
-                     double gscale, const optional<Tensor>& s1, const optional<Tensor>& s2, double lr, double beta1,
-                     double beta2, double eps, double momentum, double rho, const optional<Tensor>& beta_pow,
-                     const optional<Tensor>& global_step, int64_t gs_inc, const Tensor& done, const Tensor& blob,
-                     int64_t nseg, int64_t nwork, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
-                     int64_t wait_segs, const optional<Tensor>& clip_scale, const optional<Tensor>& sched,
-                     const optional<Tensor>& lr_out, bool nesterov, bool decay) {
-  const double hyper[6] = {lr, beta1, beta2, eps, momentum, rho};
-  dtfe::OptArgs a = opt_args(kind, p, g, g16, gscale, s1, s2, hyper, beta_pow, global_step, gs_inc, done, blob, nseg,
-                             nwork);
+void apply_gradients(const OptStateArg& o, const optional<Tensor>& g, const optional<Tensor>& g16, double gscale,
+                     double lr, int64_t gs_inc, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
+                     int64_t wait_segs, const optional<Tensor>& clip_scale) {
+  dtfe::OptArgs a = opt_launch_args(*o, g, g16, gscale, lr, gs_inc, clip_scale);
   const bool waits = wait_done.has_value() && wait_done->defined();
   TORCH_CHECK(waits == (wait_seen.has_value() && wait_seen->defined()) && (waits || wait_segs == 0),
               "apply_gradients: wait_done, wait_seen and wait_segs go together");
@@ -782,42 +823,38 @@ void apply_gradients(int64_t kind, const Tensor& p, const optional<Tensor>& g, c
     a.wait_done = wait_done->data_ptr<int>(); a.wait_seen = wait_seen->data_ptr<int>();
     a.wait_segs = (uint32_t)wait_segs;
   }
-  a.clip_scale = clip_scale_ptr(clip_scale);
-  opt_extras(a, sched, lr_out, nesterov, decay);
   dtfe::launch_apply_gradients(a, cur_stream());
 }
 
 // 2..OPT_GROUP_MAX optimizers of one kind over disjoint var lists of one parameter buffer (e.g. the GAN's
-// two Adams) in ONE grouped launch; hyper holds six floats per optimizer (lr, beta1, beta2, eps, momentum, rho)
-void apply_gradients_group(int64_t kind, const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16,
-                           double gscale, const c10::List<optional<Tensor>>& s1,
-                           const c10::List<optional<Tensor>>& s2, at::ArrayRef<double> hyper,
-                           const c10::List<optional<Tensor>>& beta_pow,
-                           const c10::List<optional<Tensor>>& global_step, at::IntArrayRef gs_inc,
-                           at::TensorList done, at::TensorList blob, at::IntArrayRef nseg, at::IntArrayRef nwork,
-                           const optional<c10::List<optional<Tensor>>>& clip_scale,
-                           const optional<c10::List<optional<Tensor>>>& sched,
-                           const optional<c10::List<optional<Tensor>>>& lr_out, at::OptionalIntArrayRef nesterov,
-                           at::OptionalIntArrayRef decay) {
-  const size_t n = done.size();
+// two Adams) in ONE grouped launch, each with its own rate, step increment and clip scale
+void apply_gradients_group(const c10::List<OptStateArg>& o, const optional<Tensor>& g, const optional<Tensor>& g16,
+                           double gscale, at::ArrayRef<double> lr, at::IntArrayRef gs_inc,
+                           const optional<c10::List<optional<Tensor>>>& clip_scale) {
+  const size_t n = o.size();
   TORCH_CHECK(n >= 1 && n <= (size_t)dtfe::OPT_GROUP_MAX, "apply_gradients_group: 1..4 optimizers");
-  TORCH_CHECK(s1.size() == n && s2.size() == n && hyper.size() == 6 * n && beta_pow.size() == n &&
-                  global_step.size() == n && gs_inc.size() == n && blob.size() == n && nseg.size() == n &&
-                  nwork.size() == n && (!clip_scale.has_value() || clip_scale->size() == n) &&
-                  (!sched.has_value() || sched->size() == n) && (!lr_out.has_value() || lr_out->size() == n) &&
-                  (!nesterov.has_value() || nesterov->size() == n) && (!decay.has_value() || decay->size() == n),
+  TORCH_CHECK(lr.size() == n && gs_inc.size() == n && (!clip_scale.has_value() || clip_scale->size() == n),
               "apply_gradients_group: one entry per optimizer in every list");
   dtfe::OptArgs q[dtfe::OPT_GROUP_MAX];
-  for (size_t i = 0; i < n; ++i) {
-    q[i] = opt_args(kind, p, g, g16, gscale, s1.get(i), s2.get(i), hyper.data() + 6 * i, beta_pow.get(i),
-                    global_step.get(i), gs_inc[i], done[i], blob[i], nseg[i], nwork[i]);
-    if (clip_scale.has_value()) q[i].clip_scale = clip_scale_ptr(clip_scale->get(i));
-    opt_extras(q[i], sched.has_value() ? sched->get(i) : optional<Tensor>(),
-               lr_out.has_value() ? lr_out->get(i) : optional<Tensor>(), nesterov.has_value() && (*nesterov)[i] != 0,
-               decay.has_value() && (*decay)[i] != 0);
-  }
+  for (size_t i = 0; i < n; ++i)
+    q[i] = opt_launch_args(*o.get(i), g, g16, gscale, lr[i], gs_inc[i],
+                           clip_scale.has_value() ? clip_scale->get(i) : optional<Tensor>());
   dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
 }
+
+}  // namespace
+
+// "apply" is apply_gradients as a method: from Python a method call costs a third of an op call that has to
+// convert the object argument (the eager launch's host cost; Optimizer.step goes this way)
+void opt_state_register() {
+  static auto cls = torch::class_<OptStateObj>("dtfe", "OptState")
+      .def(torch::init<int64_t, Tensor, optional<Tensor>, optional<Tensor>, double, double, double, double, double,
+                       optional<Tensor>, optional<Tensor>, Tensor, const Tensor&, const Tensor&, const optional<Tensor>&,
+                       optional<Tensor>, optional<Tensor>, bool, bool>())
+      .def("apply", &apply_gradients);
+}
+
+namespace {
 
 // ---------------------------------------------------------- elementwise
 int data_code(const Tensor& t) {
@@ -1528,21 +1565,15 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("head_wgrad(Tensor dl, Tensor h, Tensor(a!) dw, Tensor(b!)? db, int nc, float scale, Tensor? parts=None,"
         " Tensor(c!)? loss_sum=None, Tensor(d!)? correct=None,"
         " __torch__.torch.classes.dtfe.GemmGroup? group=None) -> ()");
-  m.def("opt_pack(Tensor segs, Tensor work, Tensor device_like, Tensor? wd=None) -> Tensor");
   m.def(
       "lr_schedule_pack(int kind, int[] bounds, float[] values, float lr, float end, int decay_steps, float inv_decay,"
       " int warmup, float inv_warmup, Tensor device_like) -> Tensor");
-  m.def(
-      "apply_gradients(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor(b!)? s1, Tensor(c!)? s2,"
-      " float lr, float beta1, float beta2, float eps, float momentum, float rho, Tensor(d!)? beta_pow,"
-      " Tensor(e!)? global_step, int gs_inc, Tensor(f!) done, Tensor blob, int nseg, int nwork,"
-      " Tensor? wait_done=None, Tensor(g!)? wait_seen=None, int wait_segs=0, Tensor? clip_scale=None,"
-      " Tensor? sched=None, Tensor(h!)? lr_out=None, bool nesterov=False, bool decay=False) -> ()");
-  m.def(
-      "apply_gradients_group(int kind, Tensor(a!) p, Tensor? g, Tensor? g16, float gscale, Tensor?[] s1, Tensor?[] s2,"
-      " float[] hyper, Tensor?[] beta_pow, Tensor?[] global_step, int[] gs_inc, Tensor[] done, Tensor[] blob,"
-      " int[] nseg, int[] nwork, Tensor?[]? clip_scale=None, Tensor?[]? sched=None, Tensor?[]? lr_out=None,"
-      " int[]? nesterov=None, int[]? decay=None) -> ()");
+  opt_state_register();
+  m.def("apply_gradients(__torch__.torch.classes.dtfe.OptState o, Tensor? g, Tensor? g16, float gscale, float lr,"
+        " int gs_inc, Tensor? wait_done=None, Tensor(a!)? wait_seen=None, int wait_segs=0, Tensor? clip_scale=None)"
+        " -> ()");
+  m.def("apply_gradients_group(__torch__.torch.classes.dtfe.OptState[] o, Tensor? g, Tensor? g16, float gscale,"
+        " float[] lr, int[] gs_inc, Tensor?[]? clip_scale=None) -> ()");
   m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
         " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
   m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
@@ -1604,8 +1635,6 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("conv_wgrad", &conv_wgrad);
   m.impl("head_xent", &head_xent);
   m.impl("head_wgrad", &head_wgrad);
-  m.impl("apply_gradients", &apply_gradients);
-  m.impl("apply_gradients_group", &apply_gradients_group);
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("scale_", &scale_);
   m.impl("gather_rows", &gather_rows);
@@ -1635,7 +1664,9 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(dtfe, CompositeExplicitAutograd, m) {
-  m.impl("opt_pack", &opt_pack);
+  // not by backend: a gradient on the wrong device reaches the op's own check
+  m.impl("apply_gradients", &apply_gradients);
+  m.impl("apply_gradients_group", &apply_gradients_group);
   m.impl("lr_schedule_pack", &lr_schedule_pack);
   m.impl("gan_head_ws_floats", &gan_head_ws_floats);
 }

@@ -400,13 +400,10 @@ class MnistCnnTrainer:
         if self.opt_fc is None:
             n_, o = self.names, self.opt
             lists = ([n_[k] for k in ("out", "bout", "bd1", "wd1")], [n_[k] for k in ("wc2", "bc2", "wc1", "bc1")])
-            self.opt_fc, self.opt_conv = (Optimizer(o.cfg, self.P, var_list=v, global_step=o.global_step)
-                                          for v in lists)
-            for s in (self.opt_fc, self.opt_conv):
-                s.s1, s.s2 = o.s1, o.s2
+            self.opt_fc, self.opt_conv = (Optimizer(o.cfg, self.P, var_list=v, global_step=o.global_step, slots_of=o,
+                                                    beta_pow=bp) for v, bp in zip(lists, (None, o.beta_pow)))
             if o.beta_pow is not None:
                 self.opt_fc.beta_pow.copy_(o.beta_pow)
-                self.opt_conv.beta_pow = o.beta_pow
 
     def apply(self):
         self.opt.step(gscale=1.0 / self.world)

@@ -10,6 +10,7 @@ distributed machinery, and as the fp32 oracle the kernel tests compare to.
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 import os
 
@@ -20,7 +21,7 @@ from ._lib import (ACT_CODES, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, KMAJ, O
                    OPT_RMSPROP, OPT_SGD, RMAJ, available, load, require)
 
 __all__ = [
-    "gemm", "linear_fwd", "conv_fwd", "conv_dgrad", "conv_wgrad", "head_xent", "apply_gradients", "opt_pack",
+    "gemm", "linear_fwd", "conv_fwd", "conv_dgrad", "conv_wgrad", "head_xent", "apply_gradients", "apply_gradients_group", "opt_state",
     "gather_rows", "uniform_fill", "cast_", "softmax_xent", "gan_loss", "mse_sigmoid", "colsum", "act_grad",
     "bias_act", "ACT_NONE", "ACT_RELU", "ACT_SIGMOID", "ACT_TANH", "ACT_CODES", "KMAJ", "RMAJ", "OPT_SGD",
     "OPT_MOMENTUM", "OPT_ADAM", "OPT_RMSPROP", "available", "load", "require", "pick_tile", "split_workspace",
@@ -778,27 +779,52 @@ def gemm_group(anchor):
 
 
 # --------------------------------------------------------------- optimizer
-def opt_pack(segs, work, device_like, wd=None):
-    """``wd``: the coupled L2 weight decay of each segment (a sequence of nseg floats); None = no decay."""
-    if wd is None:
-        return require().opt_pack(segs, work, device_like)
-    return require().opt_pack(segs, work, device_like, torch.tensor([float(x) for x in wd], dtype=torch.float32))
+def opt_state(kind, p, segs, work, done, s1=None, s2=None, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, rho=0.0,
+              beta_pow=None, global_step=None, wd=None, sched=None, lr_out=None, nesterov=False, decay=False):
+    """An optimizer bound to the native side (torch.classes.dtfe.OptState): everything that holds for its
+    life, checked once - the tensors' device, dtype and length, every segment inside ``p``, every work item
+    inside its segment - with the plan packed into a device blob.  apply_gradients then takes only what varies.
+    ``segs``: rows (off, R, T, C, w16 address, wt16 address); ``work``: rows (kind, seg, t, r0, c0, start,
+    count); ``wd``: the coupled L2 weight decay of each segment (nseg floats; None = none) - sequences or CPU
+    tensors.  ``done``: the zeroed 4-byte counter the kernel's workgroups count themselves on.
+    ``sched``: the blob of lr_schedule_pack - the kernel evaluates it at ``global_step`` and uses the result
+    in place of the launch's ``lr``; ``lr_out``: a device float32 scalar that receives the rate a launch used.
+    ``nesterov``: TF1 ApplyMomentum's use_nesterov form (momentum only).  ``decay``: launch the kernels'
+    weight-decay instantiation (some ``wd`` is non-zero); without it ``wd`` is ignored."""
+    require()
+    table = lambda t, cols: torch.as_tensor(t, dtype=torch.int64).reshape(len(t), cols)
+    if wd is not None:
+        wd = torch.as_tensor(wd, dtype=torch.float32)
+    return torch.classes.dtfe.OptState(int(kind), p, s1, s2, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
+                                       done, table(segs, 6), table(work, 7), wd, sched, lr_out, bool(nesterov),
+                                       bool(decay))
 
 
-def apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
-                    gs_inc, done, blob, nseg, nwork, wait_done=None, wait_seen=None, wait_segs=0, clip_scale=None,
-                    sched=None, lr_out=None, nesterov=False, decay=False):
-    """The launch's items of the var-list segments in bit mask ``wait_segs`` wait (on the device) until
+@functools.lru_cache(None)
+def _direct(name):
+    """The library's op ``name`` without torch.ops' Python wrapper: for an op that takes a custom class the
+    wrapper walks every argument of every call (a pytree scan for fake script objects, about 10 us - more
+    than the rest of an eager apply launch's host cost) before it enters the dispatcher.  Converting the
+    object argument costs about as much again; a method of the object pays neither."""
+    op = getattr(require(), name)
+    return getattr(op.default, "_op", op)
+
+
+def apply_gradients(state, g, g16, gscale, lr, gs_inc, wait_done=None, wait_seen=None, wait_segs=0, clip_scale=None):
+    """One launch of an ``opt_state``: exactly one of ``g`` (float32) / ``g16`` (bfloat16), contiguous, on the
+    state's GPU and at least as long as its ``p``; ``lr`` is read per launch.
+    The launch's items of the var-list segments in bit mask ``wait_segs`` wait (on the device) until
     ``wait_done`` exceeds ``wait_seen`` - a gradient produced on another stream that signals with
     epoch_signal(wait_done) instead of a stream join; the launch's last workgroup advances ``wait_seen``.
-    ``clip_scale``: a device float32 scalar multiplied into ``gscale`` by the kernel (grad_sumsq's scale).
-    ``sched``: the blob of lr_schedule_pack - the kernel evaluates it at ``global_step`` and uses the result
-    in place of ``lr``; ``lr_out``: a device float32 scalar that receives the rate the launch used.
-    ``nesterov``: TF1 ApplyMomentum's use_nesterov form (momentum only).  ``decay``: the plan was packed
-    with a non-zero weight decay on some segment (opt_pack's ``wd``); without it the decay is ignored."""
-    require().apply_gradients(kind, p, g, g16, gscale, s1, s2, lr, beta1, beta2, eps, momentum, rho, beta_pow,
-                              global_step, gs_inc, done, blob, nseg, nwork, wait_done, wait_seen, wait_segs,
-                              clip_scale, sched, lr_out, bool(nesterov), bool(decay))
+    ``clip_scale``: a device float32 scalar multiplied into ``gscale`` by the kernel (grad_sumsq's scale)."""
+    # (the op torch.ops.dtfe.apply_gradients(state, ...) as the state's method: the cheaper call, see _direct)
+    state.apply(g, g16, gscale, lr, gs_inc, wait_done, wait_seen, wait_segs, clip_scale)
+
+
+def apply_gradients_group(states, g, g16, gscale, lrs, gs_incs, clip_scales=None):
+    """Up to four ``opt_state`` of one kind (and none with a schedule) over disjoint var lists in ONE launch,
+    each with its own rate, step increment and (``clip_scales``: a list with None where there is none) clip scale."""
+    _direct("apply_gradients_group")(states, g, g16, gscale, lrs, gs_incs, clip_scales)
 
 
 # learning-rate schedules (csrc/kernels/optim.h LrSchedule / lr_schedule_eval)
@@ -861,7 +887,7 @@ def lr_schedule_value(spec, step):
 
 
 def lr_schedule_pack(spec, device_like):
-    """The device struct (a uint8 blob) of a lr_schedule_spec, for apply_gradients' ``sched``."""
+    """The device struct (a uint8 blob) of a lr_schedule_spec, for opt_state's ``sched``."""
     return require().lr_schedule_pack(spec["kind"], spec["bounds"], [float(v) for v in spec["values"]],
                                       float(spec["lr"]), float(spec["end"]), spec["decay_steps"],
                                       float(spec["inv_decay"]), spec["warmup"], float(spec["inv_warmup"]), device_like)

@@ -224,13 +224,21 @@ class Optimizer:
     ``<var>/RMSProp`` (initialised to ones), ``<var>/RMSProp_1``;
     ``<var>/Momentum``.  Adam's non-slot ``beta1_power``/``beta2_power`` are a
     2-element device tensor advanced by the kernel itself.
+
+    On the GPU the optimizer is bound to the native side once (``ops.opt_state``): plan, slots, counters
+    and the recipe are checked and fixed at construction, and of the config only ``cfg.lr`` is read at
+    every step - changing ``cfg.beta1``, ``beta2``, ``eps``, ``momentum`` or ``rho`` afterwards has no
+    effect there (the CPU path still reads them).  Likewise the tensors (``s1``, ``s2``, ``beta_pow``,
+    ``global_step``, ``done``) are bound as they are at construction: write into them, do not replace them.
     """
 
     SLOT_NAMES = {"adam": ("Adam", "Adam_1"), "rmsprop": ("RMSProp", "RMSProp_1"), "momentum": ("Momentum",),
                   "sgd": ()}
 
     def __init__(self, cfg: OptimizerConfig, params: FlatParams, var_list=None, global_step=None,
-                 beta_power_names=("beta1_power", "beta2_power")):
+                 beta_power_names=("beta1_power", "beta2_power"), slots_of=None, beta_pow=None):
+        """``slots_of``: another Optimizer over the same FlatParams whose slot buffers this one uses (disjoint
+        var lists) in place of its own; ``beta_pow``: Adam's beta powers to advance in place of an own pair."""
         self.cfg = cfg
         self.P = params
         self.kind = KINDS[cfg.kind]
@@ -241,20 +249,24 @@ class Optimizer:
         nslots = len(self.SLOT_NAMES[cfg.kind])
         # slots live in full-size flat buffers (same offsets as the masters)
         self.s1 = self.s2 = None
-        if nslots >= 1:
+        if slots_of is not None:
+            self.s1, self.s2 = slots_of.s1, slots_of.s2
+        elif nslots >= 1:
             fill = 1.0 if cfg.kind == "rmsprop" else 0.0
             self.s1 = torch.full((params.total,), fill, dtype=torch.float32, device=self.device)
-        if nslots >= 2:
-            self.s2 = torch.zeros(params.total, dtype=torch.float32, device=self.device)
-        self.beta_pow = torch.tensor([cfg.beta1, cfg.beta2], dtype=torch.float32, device=self.device) \
-            if cfg.kind == "adam" else None
+            if nslots >= 2:
+                self.s2 = torch.zeros(params.total, dtype=torch.float32, device=self.device)
+        if cfg.kind != "adam":
+            self.beta_pow = None
+        elif beta_pow is not None:
+            self.beta_pow = beta_pow
+        else:
+            self.beta_pow = torch.tensor([cfg.beta1, cfg.beta2], dtype=torch.float32, device=self.device)
         self.done = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._blob = None
+        self._state = None
         self._init_recipe()
         if self.device.type == "cuda":
             self._build_plan()
-            if self.lr_spec is not None:
-                self._sched = ops.lr_schedule_pack(self.lr_spec, params.master)
         # global-norm clipping (cfg.clip_norm > 0): the norm kernel's chunk plan, scratch and its two
         # results clip_out = [norm, scale]; the apply reads the scale from the device.  No state to save.
         self.clip_norm = float(getattr(cfg, "clip_norm", 0.0) or 0.0)
@@ -265,7 +277,7 @@ class Optimizer:
     def _init_recipe(self):
         """Schedule, weight decay and Nesterov of the config, validated; all of it off by default."""
         cfg = self.cfg
-        self.lr_spec, self._sched, self._lr_out = None, None, None
+        self.lr_spec, self._lr_out = None, None
         if cfg.has_schedule():
             if self.global_step is None:
                 raise ValueError("Optimizer: a learning-rate schedule is a function of global_step - pass one")
@@ -292,10 +304,6 @@ class Optimizer:
         """The rate the last step used (before any step: the rate of step 0) as a 1-element device tensor
         - read it on the host only when it is wanted; None without a schedule (the rate is cfg.lr)."""
         return self._lr_out
-
-    def _recipe_args(self):
-        return dict(sched=self._sched, lr_out=self._lr_out if self._sched is not None else None,
-                    nesterov=self.nesterov, decay=self.decay)
 
     # ---- plan of work items for the fused kernel
     def _build_plan(self, chunk: int = 0):
@@ -332,19 +340,20 @@ class Optimizer:
             # LDS transpose, scattered stores); dispatched last they were the launch's tail
             work.sort(key=lambda w: -w[0])
         self.nseg, self.nwork = len(segs), len(work)
-        self._tables = (segs, work)  # what the blob was packed from (tests repack it)
-        self._blob = ops.opt_pack(torch.tensor(segs, dtype=torch.int64), torch.tensor(work, dtype=torch.int64),
-                                  self.P.master, self.wd if self.decay else None)
+        self._tables = (segs, work)  # what the state was built from (tests rebuild it)
+        c = self.cfg
+        sched = ops.lr_schedule_pack(self.lr_spec, self.P.master) if self.lr_spec is not None else None
+        self._state = ops.opt_state(self.kind, self.P.master, segs, work, self.done, s1=self.s1, s2=self.s2,
+                                    beta1=c.beta1, beta2=c.beta2, eps=c.resolved_eps(), momentum=c.momentum,
+                                    rho=c.rho, beta_pow=self.beta_pow, global_step=self.global_step,
+                                    wd=self.wd if self.decay else None, sched=sched, lr_out=self._lr_out,
+                                    nesterov=self.nesterov, decay=self.decay)
 
     def _wait_mask(self, names) -> int:  # the kernel's wait_segs: 32 bits of var_list indices
         idx = [self.var_list.index(n) if n in self.var_list else -1 for n in names]
         if any(not 0 <= i < 32 for i in idx):
             raise ValueError(f"Optimizer.step(wait=...): {list(names)} must be among the first 32 of var_list")
         return sum(1 << i for i in idx)
-
-    def _hyper(self):
-        c = self.cfg
-        return [c.lr, c.beta1, c.beta2, c.resolved_eps(), c.momentum, c.rho]
 
     @property
     def global_norm(self):
@@ -370,9 +379,7 @@ class Optimizer:
         wait = (None, None, 0) if wait is None else (wait[0], wait[1], self._wait_mask(wait[2]))
         clip = self.clip.compute(grad, grad16, gscale) if self.clip is not None else None
         if self.device.type == "cuda":
-            ops.apply_gradients(self.kind, self.P.master, grad, grad16, gscale, self.s1, self.s2, *self._hyper(),
-                                self.beta_pow, self.global_step, gs_inc, self.done, self._blob, self.nseg,
-                                self.nwork, *wait, clip_scale=clip, **self._recipe_args())
+            ops.apply_gradients(self._state, grad, grad16, gscale, self.cfg.lr, gs_inc, *wait, clip_scale=clip)
             return
         self._step_cpu(grad if grad is not None else grad16.float(), gscale, gs_inc, clip)
 
@@ -394,14 +401,9 @@ class Optimizer:
             assert all(o.P is P for o in opts)
             # one norm launch per clipping optimizer, then the one grouped apply reads each one's scale
             clips = [o.clip.compute(grad, grad16, gscale) if o.clip is not None else None for o in opts]
-            ops.require().apply_gradients_group(
-                kinds.pop(), P.master, P.grad if grad is None and grad16 is None else grad, grad16, gscale,
-                [o.s1 for o in opts], [o.s2 for o in opts], [h for o in opts for h in o._hyper()],
-                [o.beta_pow for o in opts], [o.global_step for o in opts], list(gs_incs), [o.done for o in opts],
-                [o._blob for o in opts], [o.nseg for o in opts], [o.nwork for o in opts],
-                clips if any(c is not None for c in clips) else None, None, None,
-                [int(o.nesterov) for o in opts] if any(o.nesterov for o in opts) else None,
-                [int(o.decay) for o in opts] if any(o.decay for o in opts) else None)
+            ops.apply_gradients_group(
+                [o._state for o in opts], P.grad if grad is None and grad16 is None else grad, grad16, gscale,
+                [o.cfg.lr for o in opts], list(gs_incs), clips if any(c is not None for c in clips) else None)
             return
         for o, inc in zip(opts, gs_incs):
             o.step(grad=grad, grad16=grad16, gscale=gscale, gs_inc=inc)

@@ -152,11 +152,9 @@ class NativeShardService:
         g16 = self.dtype == "bf16"
         last = len(shard.opts) - 1
         for i, o in enumerate(shard.opts):
-            c = o.cfg
             gs = shard.gs if (shard.gs is not None and i == last) else None
-            lib.ps_service_add_group(self.svc, o.kind, shard.P.master, o.s1, o.s2, c.lr, c.beta1, c.beta2,
-                                     c.resolved_eps(), c.momentum, c.rho, o.beta_pow, gs,
-                                     shard.gs_increments if gs is not None else 0, o._blob, o.nseg, o.nwork, g16)
+            lib.ps_service_add_group(self.svc, o._state, o.cfg.lr, gs, shard.gs_increments if gs is not None else 0,
+                                     g16)
         if shard.gs is not None:
             lib.ps_service_set_gs(self.svc, shard.gs)
         # async: pushes arrive bucket by bucket (ranges of this shard's flat layout) and are applied

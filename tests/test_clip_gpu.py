@@ -201,9 +201,8 @@ def test_clip_norm_zero_is_the_unclipped_optimizer(kind):
     g = _fill_grad(Pa, 30)
     a.step(grad=g, gscale=0.5)
     b.step(grad=g, gscale=0.5)
-    # the op as it was called before it had a clip_scale argument
-    ops.apply_gradients(c.kind, Pc.master, g, None, 0.5, c.s1, c.s2, *c._hyper(), c.beta_pow, c.global_step, 1,
-                        c.done, c._blob, c.nseg, c.nwork)
+    # the op called without a clip_scale argument
+    ops.apply_gradients(c._state, g, None, 0.5, c.cfg.lr, 1)
     _assert_same(_state(Pa, a), _state(Pb, b))
     _assert_same(_state(Pa, a), _state(Pc, c))
 

@@ -34,7 +34,7 @@ def test_no_op_carries_state_to_a_later_call_cpu():
     if not ops.available():
         pytest.skip("native library not built")
     lib = ops.require()
-    for name in ("apply_wait_next", "wgrad_flush", "wgrad_pending", "wgrad_discard"):
+    for name in ("apply_wait_next", "wgrad_flush", "wgrad_pending", "wgrad_discard", "opt_pack"):
         assert not hasattr(lib, name), name
         assert not hasattr(ops, name), name
     assert "group" not in str(lib.apply_gradients.default._schema)

@@ -386,10 +386,8 @@ def test_head_loss_partials_fold(B, grouped):
     assert torch.equal(outs[0][0], outs[1][0])   # fixed summation order
 
 
-def _plan(n, dev):
-    segs = torch.tensor([[0, n, 1, 1, 0, 0]], dtype=torch.int64)
-    work = torch.tensor([[0, 0, 0, 0, 0, 0, n]], dtype=torch.int64)
-    return ops.opt_pack(segs, work, torch.empty(1, device=dev)), 1, 1
+def _plan(n):  # one segment, one flat work item
+    return [[0, n, 1, 1, 0, 0]], [[0, 0, 0, 0, 0, 0, n]]
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2, 3])
@@ -404,12 +402,12 @@ def test_optimizers_tf1_math(kind):
     bp = torch.tensor([0.9, 0.999], device=DEV)
     gs = torch.zeros(1, dtype=torch.int32, device=DEV)
     done = torch.zeros(1, dtype=torch.int32, device=DEV)
-    blob, ns, nw = _plan(n, DEV)
     lr, b1, b2, eps, mom, rho = 0.01, 0.9, 0.999, 1e-8, 0.5, 0.9
+    st = ops.opt_state(kind, p, *_plan(n), done, s1=s1, s2=s2, beta1=b1, beta2=b2, eps=eps if kind == 2 else 1e-10,
+                       momentum=mom, rho=rho, beta_pow=bp, global_step=gs)
     reps = 3
     for _ in range(reps):
-        ops.apply_gradients(kind, p, g.to(DEV), None, 1.0, s1, s2, lr, b1, b2, eps if kind == 2 else 1e-10, mom, rho,
-                            bp, gs, 1, done, blob, ns, nw)
+        ops.apply_gradients(st, g.to(DEV), None, 1.0, lr, 1)
     # closed form
     v = p0.clone()
     a1 = torch.ones(n) if kind == 3 else torch.zeros(n)
@@ -472,20 +470,19 @@ def test_apply_wait_arguments_do_not_outlive_their_call():
     two applies without wait arguments."""
     torch.manual_seed(11)
     n0, n1 = 3000, 2000
-    segs = torch.tensor([[0, n0, 1, 1, 0, 0], [n0, n1, 1, 1, 0, 0]], dtype=torch.int64)
-    work = torch.tensor([[0, 0, 0, 0, 0, 0, n0], [0, 1, 0, 0, 0, 0, n1]], dtype=torch.int64)
+    segs = [[0, n0, 1, 1, 0, 0], [n0, n1, 1, 1, 0, 0]]
+    work = [[0, 0, 0, 0, 0, 0, n0], [0, 1, 0, 0, 0, 0, n1]]
     p0 = torch.randn(n0 + n1, device=DEV)
     g = torch.randn(n0 + n1, device=DEV)
-    blob = ops.opt_pack(segs, work, p0)
     opt_done, done, seen = (torch.zeros(1, dtype=torch.int32, device=DEV) for _ in range(3))
     res = []
     for wait in ({}, dict(wait_done=done, wait_seen=seen, wait_segs=0b10)):
         p = p0.clone()
+        st = ops.opt_state(ops.OPT_SGD, p, segs, work, opt_done)
         if wait:
             ops.epoch_signal(done)
         for w in (wait, {}):
-            ops.apply_gradients(ops.OPT_SGD, p, g, None, 1.0, None, None, 0.1, 0, 0, 0, 0, 0, None, None, 0, opt_done,
-                                blob, 2, 2, **w)
+            ops.apply_gradients(st, g, None, 1.0, 0.1, 0, **w)
         torch.cuda.synchronize()
         res.append(p)
     assert torch.equal(res[0], res[1]) and not torch.equal(res[0], p0)
@@ -515,15 +512,14 @@ def test_optimizer_transposed_copies():
     g = torch.zeros(n, device=DEV)
     w16 = torch.empty(n, device=DEV, dtype=torch.bfloat16)
     wt16 = torch.empty(n, device=DEV, dtype=torch.bfloat16)
-    segs = torch.tensor([[0, R, T, C, w16.data_ptr(), wt16.data_ptr()]], dtype=torch.int64)
+    segs = [[0, R, T, C, w16.data_ptr(), wt16.data_ptr()]]
     work = []
     for t in range(T):
         for r0 in range(0, R, 64):
             for c0 in range(0, C, 64):
                 work.append([1, 0, t, r0, c0, 0, 0])
-    blob = ops.opt_pack(segs, torch.tensor(work, dtype=torch.int64), p)
     done = torch.zeros(1, dtype=torch.int32, device=DEV)
-    ops.apply_gradients(0, p, g, None, 1.0, None, None, 0.1, 0, 0, 0, 0, 0, None, None, 0, done, blob, 1, len(work))
+    ops.apply_gradients(ops.opt_state(0, p, segs, work, done), g, None, 1.0, 0.1, 0)
     torch.cuda.synchronize()
     assert torch.equal(w16.cpu(), p.cpu().to(torch.bfloat16))
     exp_t = p.cpu().view(R, T, C).permute(2, 1, 0).reshape(-1).to(torch.bfloat16)

@@ -205,11 +205,21 @@ def test_the_decay_is_added_after_the_clip_scale(kind):
         _assert_same(_state(Pa, a), _state(Pb, b))
 
 
+def _raw_state(o, **kw):
+    """ops.opt_state over an Optimizer's own tables and tensors, ``kw`` on top."""
+    c = o.cfg
+    segs, work = o._tables
+    args = dict(s1=o.s1, s2=o.s2, beta1=c.beta1, beta2=c.beta2, eps=c.resolved_eps(), momentum=c.momentum, rho=c.rho,
+                beta_pow=o.beta_pow, global_step=o.global_step)
+    args.update(kw)
+    return ops.opt_state(o.kind, o.P.master, segs, work, o.done, **args)
+
+
 @pytest.mark.parametrize("kind", ["sgd", "adam"])
 def test_a_plan_without_decay_is_the_old_plan(kind):
     g = None
     states = []
-    for mode in ("optimizer", "old call", "wd zeros", "wd zeros, decay kernel"):
+    for mode in ("optimizer", "no wd", "wd zeros", "wd zeros, decay kernel"):
         P = _params()
         o = _opt(P, kind)
         assert not o.decay and o.lr_spec is None
@@ -218,15 +228,10 @@ def test_a_plan_without_decay_is_the_old_plan(kind):
         if mode == "optimizer":
             o.step(grad=g, gscale=0.5)
         else:
-            blob, extra = o._blob, {}
-            if mode != "old call":
-                segs, work = o._tables
-                blob = ops.opt_pack(torch.tensor(segs, dtype=torch.int64), torch.tensor(work, dtype=torch.int64),
-                                    P.master, [0.0] * len(segs))
-                extra = dict(decay=mode.endswith("decay kernel"))
-            # the op as it was called before it had these arguments, over the 6-column plan
-            ops.apply_gradients(o.kind, P.master, g, None, 0.5, o.s1, o.s2, *o._hyper(), o.beta_pow, o.global_step,
-                                1, o.done, blob, o.nseg, o.nwork, **extra)
+            segs, work = o._tables
+            extra = {} if mode == "no wd" else dict(wd=[0.0] * len(segs), decay=mode.endswith("decay kernel"))
+            # a state of the optimizer's own tables and tensors, built without the recipe arguments
+            ops.apply_gradients(_raw_state(o, **extra), g, None, 0.5, o.cfg.lr, 1)
         states.append(_state(P, o))
     for s in states[1:]:
         _assert_same(states[0], s)
@@ -264,8 +269,7 @@ def test_nesterov_is_refused_for_other_kinds():
     P = _params()
     o = _opt(P, "sgd")
     with pytest.raises(RuntimeError, match="nesterov"):
-        ops.apply_gradients(o.kind, P.master, P.grad, None, 1.0, None, None, *o._hyper(), None, None, 1, o.done,
-                            o._blob, o.nseg, o.nwork, nesterov=True)
+        _raw_state(o, nesterov=True)
 
 
 # ------------------------------------------------------------ captured replay
@@ -345,9 +349,8 @@ def test_the_grouped_launch_decays_each_optimizers_own_segments():
         sched = ops.lr_schedule_pack(ops.lr_schedule_spec(0.1, warmup_steps=2), Pa.master)
         gs = _gs()
         ops.require().apply_gradients_group(
-            oa[0].kind, Pa.master, g, None, 1.0, [o.s1 for o in oa], [o.s2 for o in oa],
-            [h for o in oa for h in o._hyper()], [o.beta_pow for o in oa], [gs, gs], [0, 1], [o.done for o in oa],
-            [o._blob for o in oa], [o.nseg for o in oa], [o.nwork for o in oa], None, [sched, None])
+            [_raw_state(oa[0], global_step=gs, sched=sched), _raw_state(oa[1], global_step=gs)], g, None, 1.0,
+            [o.cfg.lr for o in oa], [0, 1])
 
 
 # ------------------------------------------------- next to --clip_norm / wait=
