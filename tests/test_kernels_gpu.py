@@ -142,6 +142,15 @@ def test_gemm_epilogue_bias_act_bf16_out(act):
     z = A.cpu() @ B.cpu().t() + bias.cpu()
     exp = [z, torch.relu(z), torch.sigmoid(z), torch.tanh(z)][act]
     assert _rel(out.cpu(), exp) < 1e-5
+    # the bf16 destination, against the same reference rounded to bf16: the kernel's fp32 value differs from
+    # the reference by the 1e-5 above, which can carry it across a rounding boundary - one bf16 ulp (2^-7 of
+    # the element), for few elements (the fp32 difference is a thousandth of the bf16 spacing)
+    outb = torch.full((M, N), float("nan"), device=DEV, dtype=torch.bfloat16)
+    ops.gemm(A, B, outb, M=M, N=N, K=K, bias=bias, act=act)
+    got, expb = outb.cpu().float(), exp.to(torch.bfloat16).float()
+    assert not torch.isnan(got).any()
+    assert ((got - expb).abs() <= 2.0 ** -7 * torch.maximum(got.abs(), expb.abs()) + 1e-5 * exp.abs().max()).all()
+    assert (got == expb).float().mean() > 0.99
 
 
 def test_gemm_split_k_atomic_and_aux():
