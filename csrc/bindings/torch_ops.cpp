@@ -18,6 +18,7 @@
 #include "../kernels/imgconv.h"
 #include "../kernels/norm.h"
 #include "../kernels/elementwise.h"
+#include "../kernels/eval.h"
 #include "../kernels/gemm_dense.h"
 #include "../kernels/head.h"
 #include "../kernels/lstm_seq.h"
@@ -751,6 +752,42 @@ void scale_(const Tensor& t, const Tensor& scale, const Tensor& plan) {
               "scale_: plan is a contiguous int64 [nchunk, 2] table");
   dtfe::launch_scale_ranges(t.data_ptr<float>(), scale.data_ptr<float>(),
                             reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()), (int)plan.size(0), cur_stream());
+}
+
+// one chunk of an on-device evaluation pass (kernels/eval.h)
+void eval_metrics(const Tensor& logits, const Tensor& labels, int64_t k, const Tensor& state,
+                  const optional<Tensor>& idx, const Tensor& ws, const Tensor& ticket) {
+  check_cuda(logits, "logits"); check_cuda(labels, "labels"); check_cuda(state, "state"); check_cuda(ws, "ws");
+  check_cuda(ticket, "ticket");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_contiguous() && logits.dim() == 2 && logits.size(0) >= 1 &&
+                  logits.size(1) >= 1 && logits.numel() < (int64_t(1) << 31),
+              "eval_metrics: logits are contiguous float32 [B][NC]");
+  const int64_t B = logits.size(0), NC = logits.size(1);
+  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.is_contiguous() && labels.numel() == B,
+              "eval_metrics: labels are contiguous int32 [B]");
+  TORCH_CHECK(k >= 1 && k <= NC, "eval_metrics: 1 <= k <= NC, got k = ", k, " for ", NC, " classes");
+  static_assert(sizeof(dtfe::EvalState) == dtfe::EVAL_STATE_WORDS * sizeof(int64_t), "the state is 64-bit words");
+  TORCH_CHECK(state.scalar_type() == at::kLong && state.is_contiguous() && state.numel() >= dtfe::EVAL_STATE_WORDS,
+              "eval_metrics: state is a contiguous int64 block of ", dtfe::EVAL_STATE_WORDS, " words");
+  TORCH_CHECK(ws.scalar_type() == at::kInt && ws.is_contiguous() && ws.numel() >= 2 * B,
+              "eval_metrics: the workspace holds 2 * B int32 words");
+  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "eval_metrics: int32 ticket");
+  dtfe::EvalMetricsArgs a{};
+  if (idx.has_value() && idx->defined()) {
+    check_cuda(*idx, "idx");
+    TORCH_CHECK(idx->scalar_type() == at::kInt && idx->is_contiguous() && idx->numel() >= B &&
+                    idx->get_device() == logits.get_device(),
+                "eval_metrics: idx is contiguous int32 [B] on the logits' device");
+    a.idx = idx->data_ptr<int32_t>();
+  }
+  for (const Tensor* t : {&labels, &state, &ws, &ticket})
+    TORCH_CHECK(t->get_device() == logits.get_device(), "eval_metrics: every tensor on the logits' device");
+  a.logits = logits.data_ptr<float>(); a.labels = labels.data_ptr<int32_t>();
+  a.B = (int)B; a.NC = (int)NC; a.k = (int)k;
+  a.state = reinterpret_cast<dtfe::EvalState*>(state.data_ptr());
+  a.ws = reinterpret_cast<uint32_t*>(ws.data_ptr());
+  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
+  dtfe::launch_eval_metrics(a, cur_stream());
 }
 
 // the device copy of an LrSchedule (optim.h).  kind: 0 constant, 1 piecewise, 2 linear.  The floats arrive
@@ -1577,6 +1614,8 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
         " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
   m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
+  m.def("eval_metrics(Tensor logits, Tensor labels, int k, Tensor(a!) state, Tensor(b!)? idx, Tensor(c!) ws,"
+        " Tensor(d!) ticket) -> ()");
   m.def("wgrad_tallk(Tensor A, int lda, Tensor B, int ldb, int M, int N, int K, Tensor(a!) out, int ldc,"
         " Tensor(b!)? bias, Tensor(c!) ws, int splits, float scale) -> ()");
   m.def("seq_stage(Tensor x, Tensor(a!) xh, int T, int I, Tensor ysrc, Tensor(b!) ydst, Tensor(c!)[] zero) -> ()");
@@ -1637,6 +1676,7 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("head_wgrad", &head_wgrad);
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("scale_", &scale_);
+  m.impl("eval_metrics", &eval_metrics);
   m.impl("gather_rows", &gather_rows);
   m.impl("augment_rows", &augment_rows);
   m.impl("seq_stage", &seq_stage);

@@ -724,10 +724,28 @@ class ResNetProgram(StepProgram):
         self.dfeat16 = torch.empty(B, d.cin, **bf)
         self.loss = torch.zeros(1, device=dev)
         self.correct = torch.zeros(1, dtype=torch.int32, device=dev)
-        # lowest flat offset of each block's variables: after block i's backward every gradient
-        # at or above it is final (variables are laid out in creation = forward order)
-        self.block_lo = [min(P.offsets[n] for n in b.var_names) for b in L["blocks"]]
-        self.dense_lo = min(P.offsets[d.kernel], P.offsets[d.bias])
+        # what the backward reports to a bucket hook after the head (dense_lo) and after block i (block_lo[i]):
+        # the lowest flat offset from which EVERY variable belongs to a layer whose backward has run (head,
+        # last block ... first block; the stem ends the backward with _ready(0)).  Derived from the layout
+        # itself: with the head at the front of the flat buffer (ModelDef.specs: head first, stem last) no
+        # suffix is final before the stem's gradient is, the offsets are P.total and the buckets all launch
+        # at the end of the backward - a hook that claimed more would let a bucket's all-reduce (or push)
+        # run while the backward still writes that bucket, and the replicas would drift apart
+        by_offset = sorted(((off, n) for n, off in P.offsets.items()), reverse=True)
+
+        def final_from(done):
+            lo = P.total
+            for off, n in by_offset:
+                if n not in done:
+                    break
+                lo = off
+            return lo
+        done = {d.kernel, d.bias}
+        self.dense_lo = final_from(done)
+        self.block_lo = [0] * len(L["blocks"])
+        for i in range(len(L["blocks"]) - 1, -1, -1):
+            done |= set(L["blocks"][i].var_names)
+            self.block_lo[i] = final_from(done)
         self.grad_ready = None  # optional backward-progress hook (BucketAllReduce.ready)
         self.training = True    # False inside evaluate(): no fused head (it writes gradients), no BN folds
         # (mean, inv_std) f32 [C] on the device when the training batches are standardised (--augment):
@@ -787,7 +805,14 @@ class ResNetProgram(StepProgram):
         else:
             self.y.copy_(yy)
 
-    def forward(self):
+    def forward_logits(self):
+        """The evaluation protocol of ``utils.device_eval.DeviceEvaluator``: the forward on the loaded
+        batch up to the fp32 logits [B][num_classes] (returned), with no loss, no hit counter and no
+        gradient launch.  The caller has put the BatchNorms in ``infer`` mode and set ``training`` False."""
+        self.forward(logits_only=True)
+        return self.logits
+
+    def forward(self, logits_only: bool = False):
         L = self.L
         z = L["stem"].fwd(self.x, L["stem_bn"].stats)
         if "pool_hw" in L:
@@ -802,7 +827,7 @@ class ResNetProgram(StepProgram):
         # (ResNet-20: 7 launches fewer, profiles/r5_resnet20_kernels.txt); not in evaluation (it
         # writes the dense gradients: only while training, never from evaluate())
         self.head_fused = False
-        if self.device.type == "cuda" and self.training and _HEAD_FUSE:
+        if self.device.type == "cuda" and self.training and _HEAD_FUSE and not logits_only:
             self.head_fused = ops.dense_head(self.feat16, P.view(d.kernel), P.view(d.bias), self.y, self.logits,
                                              self.loss, self.correct, P.gview(d.kernel), P.gview(d.bias),
                                              self.dfeat16, 1.0 / B)
@@ -810,6 +835,8 @@ class ResNetProgram(StepProgram):
                 return
         ops.cast_(self.feat16, self.feat)
         ops.gemm(self.feat, P.view(d.kernel), self.logits, M=B, N=d.cout, K=d.cin, bias=P.view(d.bias))
+        if logits_only:
+            return
         ops.softmax_xent(self.logits, labels_oh=self.y, scale=1.0 / B, dlogits=self.dlogits, loss_sum=self.loss,
                          correct=self.correct)
 

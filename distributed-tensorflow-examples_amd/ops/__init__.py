@@ -31,6 +31,7 @@ __all__ = [
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
     "augment_rows", "augment_draws", "AUG_SALT", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
+    "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -937,6 +938,82 @@ def scale_(t, scale, plan):
         return
     for o, n in plan.tolist():
         t[o:o + n] *= scale[0]
+
+
+# the words of an evaluation state (csrc/kernels/eval.h EvalState): int64, the last one a float64's bits
+EVAL_CURSOR, EVAL_N, EVAL_COUNT, EVAL_HITS1, EVAL_HITSK, EVAL_BAD, EVAL_LOSS = range(7)
+EVAL_STATE_WORDS = 7
+
+
+def eval_state(device, n=0):
+    """A zeroed evaluation state for a pass over ``n`` examples: int64 [EVAL_STATE_WORDS] on ``device``."""
+    st = torch.zeros(EVAL_STATE_WORDS, dtype=torch.int64)
+    st[EVAL_N] = int(n)
+    return st.to(device)
+
+
+def eval_state_dict(state) -> dict:
+    """The state's words as Python numbers (one device-to-host copy)."""
+    w = state.cpu()
+    out = {k: int(w[i]) for i, k in enumerate(("cursor", "n", "count", "hits1", "hitsk", "bad_labels"))}
+    out["loss_sum"] = float(w[EVAL_LOSS:EVAL_LOSS + 1].view(torch.float64)[0])
+    return out
+
+
+def eval_rows_ref(z, t, k):
+    """eval_metrics' per-row results on the host, float32 numpy: (loss, hit1, hitk, bad) of logits ``z``
+    [R][NC] and labels ``t`` [R].  rank = #{j: z[j] > z[t]} + #{j < t: z[j] == z[t]}; hit1 = rank == 0,
+    hitk = rank < k, both False for a NaN target or a label outside [0, NC) (``bad``).  loss =
+    (max + log(sum(exp(z - max)))) - z[t] in float32, exp and log rounded once from float64."""
+    z = np.asarray(z, dtype=np.float32)
+    t = np.asarray(t).astype(np.int64)
+    R, NC = z.shape
+    bad = (t < 0) | (t >= NC)
+    tc = np.where(bad, 0, t)
+    zt = np.where(bad, np.float32(0), z[np.arange(R), tc]).astype(np.float32)
+    j = np.arange(NC).reshape(1, NC)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rank = ((z > zt[:, None]) | ((z == zt[:, None]) & (j < t[:, None]))).sum(1)
+        ranked = ~bad & ~np.isnan(zt)
+        mx = np.fmax.reduce(z, axis=1, initial=-np.inf).astype(np.float32)
+        e = np.exp((z - mx[:, None]).astype(np.float32).astype(np.float64)).astype(np.float32)
+        se = e.sum(1, dtype=np.float32)
+        lse = (mx + np.log(se.astype(np.float64)).astype(np.float32)).astype(np.float32)
+        loss = (lse - zt).astype(np.float32)
+    return loss, ranked & (rank == 0), ranked & (rank < k), bad
+
+
+def eval_metrics(logits, labels, k, state, idx=None, ws=None, ticket=None):
+    """One chunk of an evaluation pass whose totals live in ``state`` (eval_state): with B = logits.shape[0]
+    and valid = clamp(n - cursor * B, 0, B), rows [0, valid) of fp32 ``logits`` [B][NC] and int32 ``labels``
+    [B] are scored (eval_rows_ref) and added - count, top-1 hits, top-``k`` hits, bad labels, and the losses
+    in row order in float64 - then the cursor advances and ``idx`` (int32 [B], optional) receives the next
+    chunk's rows min(cursor * B + b, n - 1).  Rows from ``valid`` on may hold anything; valid == 0 changes
+    nothing.  GPU: one launch, no host sync, bitwise reproducible; ``ws`` (int32 [2B]) and ``ticket``
+    (zeroed int32) are its scratch."""
+    B, NC = logits.shape
+    if not 1 <= int(k) <= NC:
+        raise ValueError("eval_metrics: 1 <= k <= NC, got k = %d for %d classes" % (k, NC))
+    if logits.is_cuda:
+        require().eval_metrics(logits, labels, int(k), state, idx, ws, ticket)
+        return
+    cursor, n = int(state[EVAL_CURSOR]), int(state[EVAL_N])
+    valid = max(0, min(B, n - cursor * B))
+    if valid == 0:
+        return
+    loss, hit1, hitk, bad = eval_rows_ref(logits[:valid].numpy(), labels[:valid].numpy(), int(k))
+    state[EVAL_COUNT] += valid
+    state[EVAL_HITS1] += int(hit1.sum())
+    state[EVAL_HITSK] += int(hitk.sum())
+    state[EVAL_BAD] += int(bad.sum())
+    acc = state[EVAL_LOSS:EVAL_LOSS + 1].view(torch.float64)
+    s = np.float64(acc[0].item())
+    for v in loss[~bad]:  # in row order, one float64 add per row: the kernel's fold
+        s = s + np.float64(v)
+    acc[0] = float(s)
+    state[EVAL_CURSOR] = cursor + 1
+    if idx is not None:
+        idx[:B] = torch.arange((cursor + 1) * B, (cursor + 2) * B).clamp_max(n - 1).to(idx.dtype)
 
 
 # ------------------------------------------------------------- elementwise

@@ -48,7 +48,7 @@ from .parallel.placement import round_robin
 from .parallel import ps_native
 from .parallel.ps import PSClient, PSServer, Shard, wait_for_init
 from .parallel.supervisor import Supervisor
-from .utils import flags as flagmod
+from .utils import device_eval, flags as flagmod
 from .utils.graphs import MultiStepGraph, StepGraph
 
 MODELS = {
@@ -134,6 +134,52 @@ PS_BATCHING_ERROR = ("%s: device-side shuffling and multi-step replays run in lo
                      "--mode=ps worker's step is paced by its push / pull with the ps tasks")
 CNN_SPG_ERROR = ("--steps_per_graph %d: the MNIST CNN's own schedule is captured one step per replay; pass --bucket_mb "
                  "to run the CNN on the generic path, which replays several")
+
+
+PS_EVAL_ERROR = ("--eval_every %d: periodic evaluation runs in local and all-reduce mode only - a --mode=ps worker "
+                 "holds the variables only between a pull and the next push")
+MODEL_EVAL_ERROR = ("--eval_every %d: periodic evaluation needs a program with an inference forward to logits "
+                    "(resnet20, resnet50), which model %r does not have")
+
+
+def check_eval(flags, mode=None):
+    """--eval_every against the mode, before anything is built.  (A model whose program cannot evaluate
+    is refused where the program is built, run_allreduce.)"""
+    if getattr(flags, "eval_every", 0) > 0 and mode == "ps":
+        raise ValueError(PS_EVAL_ERROR % flags.eval_every)
+
+
+def eval_metrics_row(res, topk, eval_ms) -> dict:
+    """An evaluation's result as the keys of its --metrics_jsonl row."""
+    return {"test_accuracy": res["accuracy"], "test_top%d" % topk: res["topk_accuracy"], "test_loss": res["loss"],
+            "test_examples": res["examples"], "eval_ms": eval_ms}
+
+
+@contextlib.contextmanager
+def chief_untrained_vars(model, P, world, group=None):
+    """Inside: the variables no optimizer updates (BatchNorm moving averages) hold rank 0's values on every
+    rank; on exit each rank has its own back, bit for bit.  Synchronous replicas share their trained
+    variables, but every rank's moving averages follow its own batches - evaluated with the chief's (the
+    ones its checkpoints hold), all ranks report the same numbers.  One rank: nothing happens."""
+    trained = {n for _cfg, vl, _bp in model.opt_groups for n in vl}
+    views = [P.view(s.name) for s in model.specs if s.name not in trained] if world > 1 else []
+    if not views:
+        yield
+        return
+    own = torch.cat([v.reshape(-1) for v in views])
+    chief = own.clone()
+    dist.broadcast(chief, src=0, group=group)
+
+    def put(flat):
+        o = 0
+        for v in views:
+            v.copy_(flat[o:o + v.numel()].reshape(v.shape))
+            o += v.numel()
+    put(chief)
+    try:
+        yield
+    finally:
+        put(own)
 
 
 def batching_flags(flags) -> list:
@@ -534,6 +580,9 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
     spg = max(1, int(getattr(flags, "steps_per_graph", 1)))
     dev_shuffle = getattr(flags, "shuffle", "host") == "device"
     prog = model.program(device, flags.batch_size, seed=flags.seed)
+    eval_every = max(0, int(getattr(flags, "eval_every", 0)))
+    if eval_every and not device_eval.supports(prog):
+        raise ValueError(MODEL_EVAL_ERROR % (eval_every, getattr(model, "name", "")))
     # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
     # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
     # with --clip_norm, a recipe flag or --steps_per_graph > 1, which that schedule cannot do)
@@ -597,6 +646,24 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
     # (the chief's state, broadcast above) continues the epoch order and the augmentation stream
     feeder.seek(int(gstep.item()) // model.gs_increments)
     metrics_log = MetricsLog(flags.metrics_jsonl)
+    # --eval_every: the test split resident on the device, built after the feeder (which sets the program's
+    # input statistics); every rank evaluates the whole set, with the chief's BatchNorm moving averages
+    # (chief_untrained_vars) - the trained variables are the same on every replica, so the lines agree
+    evaluator = None
+    if eval_every:
+        evaluator = device_eval.DeviceEvaluator(prog, data.test.images_u8, data.test.labels_int, topk=flags.eval_topk,
+                                                examples=flags.eval_examples, graph=flags.hip_graph)
+        prog.evaluator = evaluator  # (tests and tools read .graph / .capture_error)
+
+    def evaluate(step):
+        """One evaluation at global step ``step``: the log line, the chief's summaries, the metrics keys."""
+        t_ev = time.time()
+        with chief_untrained_vars(model, prog.P, world, group):
+            res = evaluator.run()
+        row = eval_metrics_row(res, evaluator.topk, (time.time() - t_ev) * 1000)
+        log("Global step %d Test-Accuracy: %2.4f Test-Loss: %.4f" % (step, res["accuracy"], res["loss"]))
+        sv.summary(step, {k: v for k, v in row.items() if k != "test_examples"})
+        return row
 
     state = {}
     trace = flags.trace_json if world == 1 or not flags.trace_json else \
@@ -643,7 +710,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
     begin_time = time.time()
     step = int(gstep.item())
     local_step = 0
-    capture_error_logged = graph_logged = False
+    capture_error_logged = graph_logged = evaluated = False
     try:
         while not sv.should_stop() and step < flags.num_steps:
             t0 = time.time()
@@ -690,10 +757,20 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
                 prog.check_health()
             if "m" in state:
                 model_step_hook(model, step, state["m"], log, ran)
+            # an evaluation step: a multiple of --eval_every lies among the model steps this replay ran, or
+            # training ends here (elapsed was taken above: the step's ms excludes the evaluation)
+            evaluated = False
+            if evaluator is not None:
+                ms_ = step // model.gs_increments
+                if ms_ // eval_every > (ms_ - ran) // eval_every or step >= flags.num_steps:
+                    sc.update(evaluate(step))
+                    evaluated = True
             # one line per replay: the replay's last step, ms = replay time / steps run
             metrics_log.write(step=local_step + ran - 1, gs=step, ms=elapsed * 1000, images_per_sec=ips,
                               **(dict(sc, steps=ran) if spg > 1 else sc))
             local_step += ran
+        if evaluator is not None and not evaluated:  # (stopped early, or nothing left to train)
+            evaluate(step)
         if wd is not None:  # training is over: peers may now leave at their own pace
             wd.stop()
             _leave_watchdog(store, rank, world, flags.heartbeat_timeout)
@@ -782,6 +859,7 @@ def run(model_name: str, argv=None, log=_print):
     mode = flagmod.resolve_mode(flags)  # (+ mode-dependent defaults: --heartbeat_secs)
     check_recipe(flags, model, mode)
     check_batching(flags, mode)
+    check_eval(flags, mode)
     local_rank = int(os.environ.get("LOCAL_RANK", flags.task_index if flags.job_name == "worker" else 0))
     device = resolve_device(flags.device, local_rank)
     if device.type == "cuda":

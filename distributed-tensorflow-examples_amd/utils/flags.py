@@ -154,6 +154,18 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "stays the cross-entropy alone, without the L2 term.  0 (default): off")
     add_bool(ap, "nesterov", False, "Nesterov momentum (TF1 MomentumOptimizer use_nesterov) for models that declare "
                                     "decaying variables (resnet20)")
+    ap.add_argument("--eval_every", type=int, default=0,
+                    help="evaluate on the test split whenever a multiple of N lies among the model steps an "
+                         "iteration ran, and once at the end of training (local / all-reduce modes; models whose "
+                         "program has an inference forward to logits: resnet20, resnet50).  The test set stays on "
+                         "the device, the chunks replay as one captured graph and the host reads once per "
+                         "evaluation; every rank evaluates the whole set.  The step's ms excludes the evaluation; "
+                         "its metrics line gains test_accuracy, test_top<K>, test_loss, test_examples, eval_ms.  "
+                         "0 (default): off")
+    ap.add_argument("--eval_examples", type=int, default=0,
+                    help="with --eval_every: evaluate the first M test examples only; 0 (default): the whole split")
+    ap.add_argument("--eval_topk", type=int, default=5,
+                    help="with --eval_every: K of the top-K accuracy reported next to top-1 (1 <= K <= classes)")
     ap.add_argument("--metrics_jsonl", default="", help="append {step, gs, ms, images/sec, loss} lines here")
     ap.add_argument("--heartbeat_secs", type=float, default=None,
                     help="publish a TCPStore heartbeat every N s; 0: off.  Default: %s s in --mode=allreduce "
@@ -181,6 +193,12 @@ def parse(argv=None, model_defaults=None, prog=None):
         ap.error("--weight_decay must be >= 0 (0 = off), got %r" % args.weight_decay)
     if not args.steps_per_graph >= 1:
         ap.error("--steps_per_graph must be >= 1, got %r" % args.steps_per_graph)
+    if not args.eval_every >= 0:
+        ap.error("--eval_every must be >= 0 (0 = off), got %r" % args.eval_every)
+    if not args.eval_examples >= 0:
+        ap.error("--eval_examples must be >= 0 (0 = the whole test split), got %r" % args.eval_examples)
+    if not args.eval_topk >= 1:
+        ap.error("--eval_topk must be >= 1, got %r" % args.eval_topk)
     if args.lr_end and not args.lr_decay_steps:
         ap.error("--lr_end is the end of a linear decay: it needs --lr_decay_steps")
     return args
