@@ -1285,6 +1285,8 @@ bool lstm_seq_fwd(const Tensor& xh, const Tensor& K, const Tensor& bias, double 
 
 int64_t lstm_status(bool reset) { return dtfe::lstm_split_status(reset); }
 
+int64_t lstm_last_split() { return dtfe::lstm_last_split(); }
+
 bool lstm_seq_bwd(const Tensor& K, const Tensor& act, const Tensor& c, const Tensor& dhT, const Tensor& dg,
                   int64_t I, const optional<Tensor>& dl, const optional<Tensor>& wo) {
   check_cuda(act, "act");
@@ -1530,6 +1532,7 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("lstm_seq_bwd(Tensor K, Tensor act, Tensor c, Tensor dhT, Tensor(a!) dg, int I, Tensor? dl=None,"
         " Tensor? wo=None) -> bool");
   m.def("lstm_status(bool reset=False) -> int", &lstm_status);
+  m.def("lstm_last_split() -> int", &lstm_last_split);
   m.def("bn_stats(Tensor x, Tensor(a!) stats) -> ()");
   m.def("bn_infer(Tensor x, Tensor gamma, Tensor beta, Tensor moving_mean, Tensor moving_var, float eps, int act,"
         " Tensor? res, int rstride, int OH, int OW, Tensor(a!) out) -> ()");

@@ -35,6 +35,11 @@ bool launch_lstm_seq_bwd(const LstmSeqArgs& a, hipStream_t s);
 // wrong).  Synchronises the device.  reset clears it.
 int lstm_split_status(bool reset);
 
+// what the last launch_lstm_seq_fwd / _bwd call of this process launched: 0 the single-workgroup kernel,
+// 4 / 8 the split kernel with that many workgroups per row group, -1 when it declined the shape (or
+// before any call).  A plain host-side record: a split that fell back to the single kernel shows here.
+int lstm_last_split();
+
 }  // namespace dtfe
 
 namespace dtfe {

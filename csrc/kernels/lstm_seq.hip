@@ -536,6 +536,7 @@ __global__ __launch_bounds__(LR * H / NS) void lstm_split_bwd_kernel(LstmSeqArgs
 }
 
 char* g_split_buf[64] = {};
+int g_last_split = -1;  // what the last launcher call launched: 0 single, 4 / 8 split, -1 declined
 
 SplitSync split_sync(hipStream_t s, int H) {
   char** buf = g_split_buf;
@@ -600,7 +601,10 @@ int lstm_split_status(bool reset) {
   return v;
 }
 
+int lstm_last_split() { return g_last_split; }
+
 bool launch_lstm_seq_fwd(const LstmSeqArgs& a, hipStream_t s) {
+  g_last_split = -1;
   // register-resident K slice: instantiated for the MNIST row-LSTM (I = 28, H = 128)
   if (a.H != 128 || a.I != 28 || a.B % LR || LR * a.I > 1024) return false;
   if (const int ns = split_ns(a)) {
@@ -615,7 +619,10 @@ bool launch_lstm_seq_fwd(const LstmSeqArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k, dim3(a.B / LR * NS), dim3(SPT), lds, s, a, y);
         return true;
       };
-      if (ns == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{})) return true;
+      if (ns == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{})) {
+        g_last_split = ns;
+        return true;
+      }
     }
   }
   LstmSeqArgs b = a;
@@ -627,10 +634,12 @@ bool launch_lstm_seq_fwd(const LstmSeqArgs& a, hipStream_t s) {
   auto k = lstm_seq_fwd_kernel<128, (28 + 128) / 4>;
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k, dim3(a.B / LR), dim3(1024), lds, s, b);
+  g_last_split = 0;
   return true;
 }
 
 bool launch_lstm_seq_bwd(const LstmSeqArgs& a, hipStream_t s) {
+  g_last_split = -1;
   if (a.H != 128 || a.B % LR || (a.I + a.H) % 4) return false;
   if (const int ns = split_ns(a)) {
     const SplitSync y = split_sync(s, a.H);
@@ -644,13 +653,17 @@ bool launch_lstm_seq_bwd(const LstmSeqArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k, dim3(a.B / LR * NS), dim3(SPT), lds, s, a, y);
         return true;
       };
-      if (ns == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{})) return true;
+      if (ns == 8 ? go(std::integral_constant<int, 8>{}) : go(std::integral_constant<int, 4>{})) {
+        g_last_split = ns;
+        return true;
+      }
     }
   }
   const size_t lds = ((size_t)LR * (4 * a.H + 4) + 2 * (size_t)LR * a.H) * sizeof(float);
   auto k = lstm_seq_bwd_kernel<128>;
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k, dim3(a.B / LR), dim3(1024), lds, s, a);
+  g_last_split = 0;
   return true;
 }
 
