@@ -40,6 +40,12 @@ def main():
                                           act=ops.ACT_RELU, pool=True, **t.ic1), 2.0 * B * 784 * 32 * 25),
         "conv2_fwd": (lambda: ops.imgconv(t.w["wc2"], t.p2, src=t.p1, bias=t.b["bc2"], argmax=t.a2,
                                           act=ops.ACT_RELU, pool=True, **t.ic2), conv2_flops),
+        # sampling + clearing + conv1 + conv2 in one launch (the step's forward up to fc1; compare with
+        # conv1_fwd + conv2_fwd, which leave out the sampling and the clearing)
+        "conv12_fwd": (lambda: ops.conv12_gather_fwd(t.data.images, t.data.labels, t.seed + 1, t.data_ctr, t.no_done,
+                                                     t.labels, t.x, t.w["wc1"], t.b["bc1"], t.p1, t.a1, t.accum,
+                                                     t.w["wc2"], t.b["bc2"], t.p2, t.a2),
+                       2.0 * B * 784 * 32 * 25 + conv2_flops),
         "fc1_fwd": (lambda: ops.gemm(t.p2, t.w["wd1"], t.h, M=B, N=FC, K=K1, bias=t.b["bd1"], act=ops.ACT_RELU,
                                      keep=t.keep, seed=2, counter=t.data_ctr), fc1_flops),
         "head": (lambda: ops.head_xent(t.h, t.w["out"], t.b["bout"], t.labels, t.dzf, t.dl, t.loss_sum,

@@ -335,9 +335,10 @@ bool imgconv(const optional<Tensor>& src, const optional<Tensor>& src_pooled, co
 // MNIST conv1 forward with the step's batch sampling fused in (imgconv1_copies.hip): samples B rows
 // of the uint8 dataset, writes the bf16 images to x (the weight gradient's input) and the labels,
 // clears the accumulators in `zero`, and runs conv1 + bias + ReLU + 2x2 max-pool(+argmax).
-void conv1_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
-                      const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
-                      const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax, at::TensorList zero) {
+dtfe::ImgConvArgs conv1_gather_args(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
+                                    const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
+                                    const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax,
+                                    at::TensorList zero) {
   check_cuda(images, "images");
   TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 2 && images.size(1) == 784,
               "conv1_gather_fwd: uint8 [rows][784] dataset");
@@ -364,7 +365,43 @@ void conv1_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t se
     a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
     a.zlen[a.nz++] = (long)(z.numel() * z.element_size() / 4);
   }
+  return a;
+}
+
+void conv1_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
+                      const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
+                      const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax, at::TensorList zero) {
+  const dtfe::ImgConvArgs a = conv1_gather_args(images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
+                                                argmax, zero);
   TORCH_CHECK(dtfe::launch_conv1_copies_fwd(a, cur_stream()), "conv1_gather_fwd: needs B >= 256");
+}
+
+// conv1_gather_fwd and MNIST conv2's forward (w2 [64][25][32], +bias, ReLU, 2x2 max-pool(+argmax) -> p2 / a2)
+// as ONE persistent launch (imgconv12_fused.hip): the same x, labels, p1 / a1 (y / argmax) and p2 / a2 as the
+// two launches, bit for bit.
+void conv12_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
+                       const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
+                       const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax, at::TensorList zero,
+                       const Tensor& w2, const optional<Tensor>& bias2, const Tensor& p2, const Tensor& a2) {
+  const dtfe::ImgConvArgs a = conv1_gather_args(images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
+                                                argmax, zero);
+  check_cuda(w2, "w2");
+  check_cuda(p2, "p2");
+  check_cuda(a2, "a2");
+  TORCH_CHECK(w2.scalar_type() == at::kBFloat16 && w2.is_contiguous() && w2.numel() == 64 * 25 * 32,
+              "conv12_gather_fwd: bf16 conv2 weight [64][5*5][32]");
+  TORCH_CHECK(p2.scalar_type() == at::kBFloat16 && p2.is_contiguous() && p2.numel() == (int64_t)a.B * 7 * 7 * 64,
+              "conv12_gather_fwd: bf16 p2 [B][7][7][64]");
+  TORCH_CHECK(a2.scalar_type() == at::kByte && a2.is_contiguous() && a2.numel() == p2.numel(),
+              "conv12_gather_fwd: uint8 a2 [B][7][7][64]");
+  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && argmax.scalar_type() == at::kByte && w.scalar_type() == at::kBFloat16,
+              "conv12_gather_fwd: bf16 p1 / conv1 weight, uint8 a1");
+  if (bias2.has_value() && bias2->defined())
+    TORCH_CHECK(bias2->scalar_type() == at::kFloat && bias2->numel() >= 64, "conv12_gather_fwd: fp32 conv2 bias [64]");
+  TORCH_CHECK(dtfe::launch_conv12_fused_fwd(a, reinterpret_cast<const dtfe::bf16*>(w2.data_ptr()),
+                                            ptr_or_null<float>(bias2), reinterpret_cast<dtfe::bf16*>(p2.data_ptr()),
+                                            a2.data_ptr<uint8_t>(), cur_stream()),
+              "conv12_gather_fwd: needs B >= 256");
 }
 
 // defer: the persistent kernel leaves its partial-slab reduce to a later wgrad_reduce_group and the call
@@ -1526,6 +1563,9 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("conv1_gather_fwd(Tensor images, Tensor labels_src, int seed, Tensor(a!) counter, Tensor(b!) done,"
         " Tensor(c!) labels_dst, Tensor(d!) x, Tensor w, Tensor? bias, Tensor(e!) y, Tensor(f!) argmax,"
         " Tensor(g!)[] zero) -> ()");
+  m.def("conv12_gather_fwd(Tensor images, Tensor labels_src, int seed, Tensor(a!) counter, Tensor(b!) done,"
+        " Tensor(c!) labels_dst, Tensor(d!) x, Tensor w, Tensor? bias, Tensor(e!) y, Tensor(f!) argmax,"
+        " Tensor(g!)[] zero, Tensor w2, Tensor? bias2, Tensor(h!) p2, Tensor(i!) a2) -> ()");
   m.def("lstm_seq_fwd(Tensor(a!) xh, Tensor K, Tensor bias, float forget_bias, Tensor(b!) act, Tensor(c!) c,"
         " Tensor(d!) hT, Tensor? xsrc=None, Tensor? ysrc=None, Tensor(e!)? ydst=None, Tensor(f!)? zero0=None,"
         " Tensor(g!)? zero1=None) -> bool");
@@ -1657,6 +1697,7 @@ TORCH_LIBRARY(dtfe, m) {
 
 TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("conv1_gather_fwd", &conv1_gather_fwd);
+  m.impl("conv12_gather_fwd", &conv12_gather_fwd);
   m.impl("lstm_seq_fwd", &lstm_seq_fwd);
   m.impl("lstm_seq_bwd", &lstm_seq_bwd);
   m.impl("bn_stats", &bn_stats);

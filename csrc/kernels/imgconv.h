@@ -119,6 +119,12 @@ bool launch_imgwgrad_persistent(const ImgWgradArgs& a, hipStream_t s, WpReduceIt
 // (imgconv1_copies.hip); false when the shape is not that layer
 bool launch_conv1_copies_fwd(const ImgConvArgs& a, hipStream_t s);
 bool launch_conv1_copies_wgrad(const ImgWgradArgs& a, hipStream_t s);
+// MNIST conv1 (with the fused batch sampling: a.g_src set, a.y / a.argmax = p1 / a1) and conv2
+// (w2 [64][25][32], bias b2, +ReLU, 2x2 max-pool -> p2 / a2 [B][7][7][64]) forward as ONE persistent
+// launch (imgconv12_fused.hip), bit-identical to launch_conv1_copies_fwd followed by conv2's
+// persistent forward; false when the arguments are not that pair (B >= 256, ReLU, pooled)
+bool launch_conv12_fused_fwd(const ImgConvArgs& a, const bf16* w2, const float* b2, bf16* p2, uint8_t* a2,
+                             hipStream_t s);
 
 
 // dw[k] += scale * sum_{p < nblk} ws[p * len + k]   (k >= nw: db[k - nw]), len % 4 == 0.

@@ -195,7 +195,11 @@ class MnistCnnTrainer:
         # ONE schedule per world size (every measured-slower alternative was removed in round 4;
         # their A/B tables stay in profiles/r2_cnn_branch_orders.txt, r2_cnn_head_fuse_ab.txt,
         # r3_cnn_kernel_tuning.txt, r3_cnn_c2_after_ab.txt, r3_cnn_fused_adam_ab.txt):
-        #   * batch sampling + accumulator clearing + conv1 in one launch (standalone, B >= 256);
+        #   * batch sampling + accumulator clearing + conv1 + conv2 in ONE persistent launch (standalone,
+        #     B >= 256; ops.conv12_gather_fwd, csrc/kernels/imgconv12_fused.hip: conv1's pooled output goes
+        #     straight into conv2's LDS image, conv2's weights are staged once per workgroup for both -
+        #     profiles/conv12_fused_fwd.txt); fed batches, evaluation and B < 256 run conv1 (with the
+        #     sampling fused where there is any) and conv2 as two launches;
         #   * the fc backward (head weight gradient, fc1 data + weight gradients) as ONE grouped
         #     launch on the main stream;
         #   * conv2's data gradient on the main stream, its weight gradient (192 workgroups, own
@@ -210,6 +214,7 @@ class MnistCnnTrainer:
         # (test hooks, not knobs: the separate gather launch and the whole-model apply with an
         # all-reduce attached are the oracles the fused / split schedule is checked against)
         self.fused_gather = True
+        self.fused_conv12 = True   # (off: conv1_gather_fwd + conv2's own launch, the oracle of the fused one)
         self.late_split = True
         # fc1 GEMMs on the global_load_lds tiles (gemm_glds.h) where the shapes allow: the forward
         # (one 64x64 tile per CU, 49 k-tiles) with two 4-wave k-groups per workgroup, 3 stages each
@@ -286,8 +291,14 @@ class MnistCnnTrainer:
             (k = 1, 2, ...) has its dropout mask at c = k; ``evaluate`` restores c."""
         B = self.B
         keep = self.keep if keep is None else keep
-        if self.data is not None and self.device.type == "cuda" and B >= 256 and self.fused_gather:
-            # standalone: batch sampling, accumulator clearing and conv1 in ONE launch
+        fused = self.data is not None and self.device.type == "cuda" and B >= 256 and self.fused_gather
+        if fused and self.fused_conv12:
+            # standalone: batch sampling, accumulator clearing, conv1 and conv2 in ONE launch
+            ops.conv12_gather_fwd(self.data.images, self.data.labels, self.seed + 1, self.data_ctr, self.no_done,
+                                  self.labels, self.x, self.w["wc1"], self.b["bc1"], self.p1, self.a1, self.accum,
+                                  self.w["wc2"], self.b["bc2"], self.p2, self.a2)
+        elif fused:
+            # batch sampling, accumulator clearing and conv1 in ONE launch
             # (the sampling counter is advanced by head_xent, after its last reader: fc1's dropout -
             # a grid-wide last-arriver atomic here serialised ~10 us of the launch)
             ops.require().conv1_gather_fwd(self.data.images, self.data.labels, self.seed + 1, self.data_ctr,
@@ -302,8 +313,9 @@ class MnistCnnTrainer:
                     t.zero_()
             ops.imgconv(self.w["wc1"], self.p1, src=self.x, bias=self.b["bc1"], argmax=self.a1, act=ops.ACT_RELU,
                         pool=True, **self.ic1)
-        ops.imgconv(self.w["wc2"], self.p2, src=self.p1, bias=self.b["bc2"], argmax=self.a2, act=ops.ACT_RELU,
-                    pool=True, **self.ic2)
+        if not (fused and self.fused_conv12):
+            ops.imgconv(self.w["wc2"], self.p2, src=self.p1, bias=self.b["bc2"], argmax=self.a2, act=ops.ACT_RELU,
+                        pool=True, **self.ic2)
         K1 = 7 * 7 * C2
         ops.gemm(self.p2, self.w["wd1"], self.h, M=B, N=FC, K=K1, bias=self.b["bd1"], act=ops.ACT_RELU,
                  keep=keep, seed=self.seed + 2, counter=self.data_ctr, tile=self.t_fwd)

@@ -509,6 +509,19 @@ def imgconv(w, y, *, B, SH, SW, CS, OH, OW, N, KH, KW, stride=1, pad=0, src=None
     return y
 
 
+def conv12_gather_fwd(images, labels_src, seed, counter, done, labels_dst, x, w1, b1, p1, a1, zero, w2, b2, p2, a2):
+    """MNIST CNN forward up to fc1 in ONE persistent launch (GPU only, B >= 256; a missing kernel is an
+    error): the step's batch sampling (``conv1_gather_fwd``'s arguments: uint8 ``images`` [rows][784],
+    ``labels_src``, ``seed``, ``counter``; ``done`` empty = the counter is advanced later in the step;
+    ``zero``: up to 4 accumulators cleared), conv1 + bias + ReLU + 2x2 max-pool -> ``p1`` / ``a1``, conv2 +
+    bias + ReLU + 2x2 max-pool -> ``p2`` / ``a2``.  Bit-identical to conv1_gather_fwd followed by conv2's
+    imgconv (csrc/kernels/imgconv12_fused.hip)."""
+    if not p2.is_cuda:
+        raise RuntimeError("conv12_gather_fwd: GPU only (the CPU path runs gather_rows and imgconv)")
+    require().conv12_gather_fwd(images, labels_src, seed, counter, done, labels_dst, x, w1, b1, p1, a1, list(zero),
+                                w2, b2, p2, a2)
+
+
 def imgconv_shortcut(w, dx, g, sc_stride, *, src, **geom) -> bool:
     """Data gradient of a whole-image conv (flipped taps over ``src`` = dY, ``geom`` as for
     imgconv(flip_taps=True)) with the option-A shortcut's gradient added in the same launch:
