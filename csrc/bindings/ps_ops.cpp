@@ -397,6 +397,8 @@ void ps_service_add_group(int64_t h, const c10::intrusive_ptr<OptStateObj>& o, d
   Service* s = svc_of(h);
   TORCH_CHECK(!o->args.sched && !o->args.nesterov && !o->args.decay,
               "dtfe ps: the service applies the plain optimizers (no schedule, Nesterov or weight decay)");
+  // the service writes reply destinations (w16b, wt16b, pb, rep_slot) and applies bucket by bucket
+  TORCH_CHECK(!o->args.ema, "dtfe ps: the service applies the plain optimizers (no EMA)");
   Group g{};
   g.opt = o;
   g.args = o->args;  // done_counter is set per launch (each worker channel has its own)

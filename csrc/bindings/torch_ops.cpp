@@ -628,7 +628,8 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
                          double eps, double momentum, double rho, optional<Tensor> beta_pow,
                          optional<Tensor> global_step, Tensor done, const Tensor& segs_t, const Tensor& work_t,
                          const optional<Tensor>& wd, optional<Tensor> sched, optional<Tensor> lr_out, bool nesterov,
-                         bool decay) {
+                         bool decay, optional<Tensor> ema, double ema_decay, bool ema_num_updates,
+                         optional<Tensor> ema_out) {
   TORCH_CHECK(kind >= dtfe::OPT_SGD && kind <= dtfe::OPT_RMSPROP, "OptState: kind is 0 (sgd) .. 3 (rmsprop)");
   check_cuda(p, "p");
   TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous(), "OptState: p is contiguous float32");
@@ -667,6 +668,19 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
   TORCH_CHECK(!nesterov || kind == dtfe::OPT_MOMENTUM, "OptState: nesterov is for the momentum optimizer");
   a.nesterov = nesterov ? 1 : 0;
   a.decay = decay ? 1 : 0;
+  // the shadow buffer of an exponential moving average: full size, p's offsets
+  a.ema = (float*)bind(ema, "ema", is(ema, at::kFloat), "float32", numel, true);
+  a.ema_out = (float*)bind(ema_out, "ema_out", is(ema_out, at::kFloat), "float32", 1, false);
+  if (a.ema) {
+    TORCH_CHECK(a.ema != a.p, "OptState: ema is a buffer of its own, not p");
+    TORCH_CHECK(ema_decay >= 0.0 && (float)ema_decay < 1.f, "OptState: ema_decay lies in [0, 1), got ", ema_decay);
+    TORCH_CHECK(!ema_num_updates || a.global_step, "OptState: ema_num_updates needs a global_step");
+    a.ema_decay = (float)ema_decay;
+    a.ema_num_updates = ema_num_updates ? 1 : 0;
+  } else {
+    TORCH_CHECK(!a.ema_out && !ema_num_updates && ema_decay == 0.0, "OptState: ema_decay, ema_num_updates and ema_out "
+                "need the ema buffer");
+  }
 
   auto table = [](const Tensor& t, const char* name, int64_t cols) {
     TORCH_CHECK(t.device().is_cpu() && t.scalar_type() == at::kLong && t.dim() == 2 && t.size(1) == cols, "OptState: ",
@@ -916,6 +930,13 @@ void apply_gradients_group(const c10::List<OptStateArg>& o, const optional<Tenso
   dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
 }
 
+// exchanges the masters of the optimizer's var list with their EMA shadows and rewrites the bf16 copies from
+// the new masters (kernels/optim.h launch_ema_swap); every pointer was checked when the state was built
+void ema_swap(const OptStateArg& o) {
+  TORCH_CHECK(o->args.ema, "ema_swap: the optimizer has no EMA (OptState built without an ema buffer)");
+  dtfe::launch_ema_swap(o->args, cur_stream());
+}
+
 }  // namespace
 
 // "apply" is apply_gradients as a method: from Python a method call costs a third of an op call that has to
@@ -924,8 +945,10 @@ void opt_state_register() {
   static auto cls = torch::class_<OptStateObj>("dtfe", "OptState")
       .def(torch::init<int64_t, Tensor, optional<Tensor>, optional<Tensor>, double, double, double, double, double,
                        optional<Tensor>, optional<Tensor>, Tensor, const Tensor&, const Tensor&, const optional<Tensor>&,
-                       optional<Tensor>, optional<Tensor>, bool, bool>())
-      .def("apply", &apply_gradients);
+                       optional<Tensor>, optional<Tensor>, bool, bool, optional<Tensor>, double, bool,
+                       optional<Tensor>>())
+      .def("apply", &apply_gradients)
+      .def("ema_swap", &ema_swap);
 }
 
 namespace {
@@ -1654,6 +1677,7 @@ TORCH_LIBRARY(dtfe, m) {
         " -> ()");
   m.def("apply_gradients_group(__torch__.torch.classes.dtfe.OptState[] o, Tensor? g, Tensor? g16, float gscale,"
         " float[] lr, int[] gs_inc, Tensor?[]? clip_scale=None) -> ()");
+  m.def("ema_swap(__torch__.torch.classes.dtfe.OptState o) -> ()");
   m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
         " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
   m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
@@ -1751,6 +1775,7 @@ TORCH_LIBRARY_IMPL(dtfe, CompositeExplicitAutograd, m) {
   // not by backend: a gradient on the wrong device reaches the op's own check
   m.impl("apply_gradients", &apply_gradients);
   m.impl("apply_gradients_group", &apply_gradients_group);
+  m.impl("ema_swap", &ema_swap);
   m.impl("lr_schedule_pack", &lr_schedule_pack);
   m.impl("gan_head_ws_floats", &gan_head_ws_floats);
 }

@@ -104,7 +104,30 @@ struct OptArgs {
   float* lr_out;            // nullable: the last workgroup stores the rate this launch used
   int nesterov;             // OPT_MOMENTUM: TF1 ApplyMomentum's use_nesterov form
   int decay;                // 1: some segment has wd != 0 (the kernels' weight-decay instantiation)
+  // optional exponential moving average of the var list (tf.train.ExponentialMovingAverage), nullable: a
+  // full-size flat buffer with p's offsets.  Every element the launch stores to p also updates its shadow,
+  // shadow -= (shadow - p) * (1 - d), with d = ema_decay or, with ema_num_updates,
+  // min(ema_decay, (1 + n) / (10 + n)) at n = *global_step + gs_inc (the step after this launch's advance).
+  // Null: the kernels' instantiation without it, and the arithmetic is exactly as before there was one
+  float* ema;
+  float ema_decay;
+  int ema_num_updates;
+  float* ema_out;           // nullable: the last workgroup stores the decay this launch used
 };
+
+// the decay of a launch and one element's update (TF1 assign_moving_average), fp32 with no contraction:
+// a numpy-float32 host mirror (ops.ema_decay_value / ops.ema_update_ref) gives the same bits - the one
+// division is IEEE-rounded (hipcc's default for fp32 division)
+__host__ __device__ __forceinline__ float ema_decay_eval(float decay, int num_updates, int n) {
+#pragma clang fp contract(off)
+  if (!num_updates) return decay;
+  const float r = (float)(1 + n) / (float)(10 + n);
+  return r < decay ? r : decay;
+}
+__host__ __device__ __forceinline__ float ema_update(float shadow, float v, float omd) {
+#pragma clang fp contract(off)
+  return shadow - (shadow - v) * omd;
+}
 // points a.segs / a.work into a plan blob of nseg segments
 inline void opt_blob_plan(const void* blob, size_t nseg, OptArgs& a) {
   a.segs = reinterpret_cast<const OptSeg*>(blob);
@@ -114,6 +137,9 @@ inline void opt_blob_plan(const void* blob, size_t nseg, OptArgs& a) {
 void launch_epoch_signal(int* ctr, hipStream_t s);
 
 void launch_apply_gradients(const OptArgs& a, hipStream_t s);
+// exchanges p and ema over the optimizer's plan (a.segs / a.work) and rewrites the bf16 copies from the new
+// p, as the apply lays them out; slots, step and counters are not touched.  Two swaps restore every buffer
+void launch_ema_swap(const OptArgs& a, hipStream_t s);
 // the non-slot scalars of one optimizer step: beta powers (Adam) and global_step += gs_inc
 void launch_opt_advance(const OptArgs& a, hipStream_t s);
 // the step scalars of n (<= OPT_GROUP_MAX) optimizers and then, if a[n-1].rep_slot is set, its

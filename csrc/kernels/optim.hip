@@ -14,7 +14,9 @@
 //               (ms slot initialised to ONES by the host)
 //   Nesterov  : a = m*a + g ; v -= g*lr + (a*m)*lr            (ApplyMomentum, use_nesterov)
 // Optional, all inside the same launch: lr from a schedule evaluated at global_step
-// (OptArgs::sched), and a coupled L2 term per segment, g = g*scale + wd*v (OptSeg::wd).
+// (OptArgs::sched), a coupled L2 term per segment, g = g*scale + wd*v (OptSeg::wd), and an exponential
+// moving average of the updated values, shadow -= (shadow - v) * (1 - decay) (OptArgs::ema); ema_swap_kernel
+// exchanges the two buffers to evaluate with the average.
 //
 // Memory-bound: the flat path moves 4 elements per thread per iteration with
 // 16-byte loads/stores of every stream (p, g, slots) and 8-byte bf16 stores.
@@ -26,6 +28,7 @@ namespace dtfe {
 // Adam multiplies with (lr with the bias correction folded in), lr itself for the other kinds
 struct OptRate {
   float lr, lr_t;
+  float omd;  // the EMA instantiations: 1 - decay of this launch (unused, and no register, in the others)
 };
 
 template <int KIND, bool NAG>
@@ -93,7 +96,7 @@ __device__ __forceinline__ void store_copies(const f32x4_t& p, bf16* w16, bf16* 
   if (pb) *reinterpret_cast<f32x4_t*>(pb) = p;
 }
 
-template <int KIND, bool G16, bool WD, bool NAG>
+template <int KIND, bool G16, bool WD, bool NAG, bool EMA>
 __device__ __forceinline__ void update_vec4(const OptArgs& a, OptRate rt, float gs, float wd, long i, bf16* w16, bf16* w16b,
                                             float* pb) {
   f32x4_t g;
@@ -108,25 +111,29 @@ __device__ __forceinline__ void update_vec4(const OptArgs& a, OptRate rt, float 
   f32x4_t s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
   if (KIND != OPT_SGD) s1 = *reinterpret_cast<const f32x4_t*>(a.s1 + i);
   if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) s2 = *reinterpret_cast<const f32x4_t*>(a.s2 + i);
+  f32x4_t e = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (EMA) e = *reinterpret_cast<const f32x4_t*>(a.ema + i);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float x1 = s1[j], x2 = s2[j];
     p[j] = upd<KIND, NAG>(a, rt, p[j], scaled_grad<WD>(g[j], gs, wd, p[j]), x1, x2);
     s1[j] = x1;
     s2[j] = x2;
+    if constexpr (EMA) e[j] = ema_update(e[j], p[j], rt.omd);
   }
   *reinterpret_cast<f32x4_t*>(a.p + i) = p;
   if (KIND != OPT_SGD) *reinterpret_cast<f32x4_t*>(a.s1 + i) = s1;
   if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) *reinterpret_cast<f32x4_t*>(a.s2 + i) = s2;
+  if constexpr (EMA) *reinterpret_cast<f32x4_t*>(a.ema + i) = e;
   store_copies(p, w16, w16b, pb);
 }
 
 // U vec4 updates at i, i+1024, ... (one workgroup-wide stride apart): every load is issued
-// before the first update, so each thread keeps U x (3-4) 16-B loads in flight
-template <int KIND, int U, bool G16, bool WD, bool NAG>
+// before the first update, so each thread keeps U x (3-4) 16-B loads in flight (one more with EMA)
+template <int KIND, int U, bool G16, bool WD, bool NAG, bool EMA>
 __device__ __forceinline__ void update_vec4x(const OptArgs& a, OptRate rt, float gs, float wd, long i, bf16* w16, bf16* w16b,
                                              float* pb) {
-  f32x4_t g[U], p[U], s1[U], s2[U];
+  f32x4_t g[U], p[U], s1[U], s2[U], e[EMA ? U : 1];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const long k = i + u * 1024;
@@ -141,6 +148,7 @@ __device__ __forceinline__ void update_vec4x(const OptArgs& a, OptRate rt, float
     s1[u] = s2[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     if (KIND != OPT_SGD) s1[u] = *reinterpret_cast<const f32x4_t*>(a.s1 + k);
     if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) s2[u] = *reinterpret_cast<const f32x4_t*>(a.s2 + k);
+    if constexpr (EMA) e[u] = *reinterpret_cast<const f32x4_t*>(a.ema + k);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -151,20 +159,38 @@ __device__ __forceinline__ void update_vec4x(const OptArgs& a, OptRate rt, float
       p[u][j] = upd<KIND, NAG>(a, rt, p[u][j], scaled_grad<WD>(g[u][j], gs, wd, p[u][j]), x1, x2);
       s1[u][j] = x1;
       s2[u][j] = x2;
+      if constexpr (EMA) e[u][j] = ema_update(e[u][j], p[u][j], rt.omd);
     }
     *reinterpret_cast<f32x4_t*>(a.p + k) = p[u];
     if (KIND != OPT_SGD) *reinterpret_cast<f32x4_t*>(a.s1 + k) = s1[u];
     if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) *reinterpret_cast<f32x4_t*>(a.s2 + k) = s2[u];
+    if constexpr (EMA) *reinterpret_cast<f32x4_t*>(a.ema + k) = e[u];
     store_copies(p[u], w16 ? w16 + u * 1024 : nullptr, w16b ? w16b + u * 1024 : nullptr, pb ? pb + u * 1024 : nullptr);
   }
 }
 
+// How many vec4 updates a thread of the flat path keeps in flight.  Without EMA: 4, as ever.  The EMA
+// instantiations hold one more 16-byte array per update in flight (Adam / RMSProp: five - g, p, two slots,
+// shadow - 20 VGPRs each).  The compiler's register report (-Rpass-analysis=kernel-resource-usage) at 4 in
+// flight, without -> with EMA: Adam 140 -> 166 and RMSProp 135 -> 158 VGPRs, both still 3 waves per SIMD
+// (the step to 2 is past 170) and no scratch; momentum 112 -> 133 (4 -> 3 waves), SGD 96 -> 114 (5 -> 4).
+// Compiled with 2 in flight, SGD and momentum report the same counts (114 and 134): the instantiation's
+// registers are set by the transposed-tile path, whose 16 elements per thread now carry a shadow each, not
+// by this body - a smaller unroll buys no wave back and only takes loads out of flight.  So: 4 for every
+// kind, chosen from the register counts, not from a timing of each choice; bench/ema_apply_bench.py times
+// the result against the stock second pass (profiles/ema_apply.txt).
+template <int KIND, bool EMA>
+__device__ constexpr int ema_unroll() {
+  return 4;
+}
+
 // One optimizer's share of a launch: workgroups bid = 0..nblk-1 of the grid (the whole grid for a
 // plain launch, a contiguous range of it for a grouped one).
-// lr: the launch's learning rate (launch_rate).
-template <int KIND, bool G16, bool WD, bool NAG>
-__device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid, int nblk, bf16 (&tile)[64][66]) {
-  OptRate rt{lr, lr};
+// lr: the launch's learning rate (launch_rate); omd: 1 - the launch's EMA decay (launch_ema_decay).
+template <int KIND, bool G16, bool WD, bool NAG, bool EMA>
+__device__ __forceinline__ void apply_items(const OptArgs& a, float lr, float omd, int bid, int nblk,
+                                            bf16 (&tile)[64][66]) {
+  OptRate rt{lr, lr, omd};
   if (KIND == OPT_ADAM) rt.lr_t = tf1_adam_lr(lr, a.beta_pow);
   // the gradient scale of this launch: the host's, times the device scalar of a global-norm clip
   // (grad_sumsq_kernel's out[1], written by the launch before this one on the stream)
@@ -194,14 +220,17 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid,
       long j = threadIdx.x * 4;
       auto at16 = [&](bf16* q, long jj) { return q ? q + w.start + jj : nullptr; };
       auto at32 = [&](float* q, long jj) { return q ? q + w.start + jj : nullptr; };
-      for (; j + 3 * 1024 < n4; j += 4 * 1024)  // 4 independent vec4 updates in flight per thread
-        update_vec4x<KIND, 4, G16, WD, NAG>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+      constexpr int U = ema_unroll<KIND, EMA>();  // independent vec4 updates in flight per thread: 4 without EMA
+      for (; j + (U - 1) * 1024 < n4; j += U * 1024)
+        update_vec4x<KIND, U, G16, WD, NAG, EMA>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j),
+                                                 at32(sg.pb, j));
       for (; j < n4; j += 256 * 4)
-        update_vec4<KIND, G16, WD, NAG>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
+        update_vec4<KIND, G16, WD, NAG, EMA>(a, rt, gs, sg.wd, base + j, at16(sg.w16, j), at16(sg.w16b, j), at32(sg.pb, j));
       for (long j = n4 + threadIdx.x; j < w.count; j += 256) {
         const long li = w.start + j, i = sg.off + li;
         const float p = a.p[i];
         const float v = update_one<KIND, NAG>(a, rt, i, p, scaled_grad<WD>(load_grad<G16>(a, i), gs, sg.wd, p));
+        if constexpr (EMA) a.ema[i] = ema_update(a.ema[i], v, rt.omd);
         if (sg.w16) sg.w16[li] = f2bf(v);
         if (sg.w16b) sg.w16b[li] = f2bf(v);
         if (sg.pb) sg.pb[li] = v;
@@ -212,7 +241,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid,
       // alias later loads, so a per-element loop ran 16 dependent HBM round trips per workgroup)
       const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
       const int c = w.c0 + tx;
-      float gv[16], pv[16], s1v[16], s2v[16];
+      float gv[16], pv[16], s1v[16], s2v[16], ev[EMA ? 16 : 1];
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int r = w.r0 + ty + 4 * u;
@@ -223,6 +252,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid,
         gv[u] = scaled_grad<WD>(load_grad<G16>(a, i), gs, sg.wd, pv[u]);
         s1v[u] = KIND != OPT_SGD ? a.s1[i] : 0.f;
         s2v[u] = (KIND == OPT_ADAM || KIND == OPT_RMSPROP) ? a.s2[i] : 0.f;
+        if constexpr (EMA) ev[u] = a.ema[i];
       }
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
@@ -234,6 +264,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, int bid,
           a.p[i] = v;
           if (KIND != OPT_SGD) a.s1[i] = x1;
           if (KIND == OPT_ADAM || KIND == OPT_RMSPROP) a.s2[i] = x2;
+          if constexpr (EMA) a.ema[i] = ema_update(ev[u], v, rt.omd);
           const bf16 b = f2bf(v);
           if (sg.w16) sg.w16[li] = b;
           if (sg.w16b) sg.w16b[li] = b;
@@ -277,6 +308,20 @@ __device__ __forceinline__ float launch_rate(const OptArgs& a) {
   return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scheduled_rate(a.sched, a.global_step))));
 }
 
+// The EMA decay of a launch, read by every workgroup where the rate is: before its first item, so every
+// workgroup of the launch sees the step the launch starts from.  With num_updates the decay is a function
+// of the step AFTER this launch's advance (TF runs the EMA op after minimize has incremented the step).
+// Out of line for scheduled_rate's reason: the division's dozen instructions are cold code.
+__device__ __noinline__ float stepped_ema_decay(float decay, int32_t* global_step, int gs_inc) {
+  const int step = __hip_atomic_load(global_step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return ema_decay_eval(decay, 1, __builtin_amdgcn_readfirstlane(step) + gs_inc);
+}
+__device__ __forceinline__ float launch_ema_decay(const OptArgs& a) {
+  if (!a.ema_num_updates) return a.ema_decay;
+  return __uint_as_float(
+      __builtin_amdgcn_readfirstlane(__float_as_uint(stepped_ema_decay(a.ema_decay, a.global_step, a.gs_inc))));
+}
+
 // the ps reply words (ps_link.h PsWord: REP_GS 9, REP_VER 10, REP_STALE 11, REP_SEQ 8 last) into
 // the worker's slot of the host-mapped shared page: system-scope relaxed stores (they go to the
 // page, no cache holds them), the sequence number only after the others have completed - no
@@ -295,12 +340,15 @@ __device__ __forceinline__ void publish_reply(const OptArgs& a) {
 
 // WD: the weight-decay instantiation, launched only when some segment decays (OptArgs::decay); NAG: the
 // one with the Nesterov branch (OptArgs::nesterov).  A launch with neither runs the kernel, and the
-// arithmetic, it ran before there was either
-template <int KIND, bool WD, bool NAG>
+// arithmetic, it ran before there was either.  EMA: the one that also updates the shadow buffer
+// (OptArgs::ema), launched only when there is one - the same rule
+template <int KIND, bool WD, bool NAG, bool EMA>
 __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, bf16 (&tile)[64][66]) {
+#pragma clang fp contract(off)
   const float lr = launch_rate(a);
-  if (a.g) apply_items<KIND, false, WD, NAG>(a, lr, bid, nblk, tile);
-  else apply_items<KIND, true, WD, NAG>(a, lr, bid, nblk, tile);
+  const float d = EMA ? launch_ema_decay(a) : 0.f;
+  if (a.g) apply_items<KIND, false, WD, NAG, EMA>(a, lr, 1.f - d, bid, nblk, tile);
+  else apply_items<KIND, true, WD, NAG, EMA>(a, lr, 1.f - d, bid, nblk, tile);
   // last workgroup: advance the non-slot scalars.  Every thread read them at its start and
   // used the value; after the barrier one lane takes a ticket (relaxed agent atomics - nothing
   // is handed between workgroups, so no fences) and the last arriver updates them.
@@ -313,6 +361,7 @@ __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, 
     const uint32_t prev = __hip_atomic_fetch_add(a.done_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // the rate this launch used, for logging: stored before the step it was computed from advances
     if (prev == (uint32_t)nblk - 1 && a.lr_out) *a.lr_out = lr;
+    if (EMA && prev == (uint32_t)nblk - 1 && a.ema_out) *a.ema_out = d;
     if (prev == (uint32_t)nblk - 1 && !a.skip_advance) {
       if (KIND == OPT_ADAM) {
         a.beta_pow[0] *= a.beta1;
@@ -327,10 +376,10 @@ __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, 
   }
 }
 
-template <int KIND, bool WD, bool NAG>
+template <int KIND, bool WD, bool NAG, bool EMA>
 __global__ __launch_bounds__(256) void apply_gradients_kernel(OptArgs a) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
-  apply_body<KIND, WD, NAG>(a, blockIdx.x, gridDim.x, tile);
+  apply_body<KIND, WD, NAG, EMA>(a, blockIdx.x, gridDim.x, tile);
 }
 
 // Several optimizers of one kind in ONE launch (the GAN's two Adams over disjoint var lists):
@@ -338,12 +387,13 @@ __global__ __launch_bounds__(256) void apply_gradients_kernel(OptArgs a) {
 // beta powers and global-step increment, exactly as separate launches would.
 // Not for optimizers with a schedule that share a global step: one optimizer's last workgroup may
 // advance the step before another's workgroups have read it (launch_apply_gradients_group refuses).
+// Nor, for the same reason, for optimizers with an EMA: the group kernels have no EMA instantiation.
 template <int KIND, bool WD, bool NAG>
 __global__ __launch_bounds__(256) void apply_gradients_group_kernel(OptGroup g) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
   int i = 0;
   while (i + 1 < g.n && (int)blockIdx.x >= g.first[i + 1]) ++i;
-  apply_body<KIND, WD, NAG>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
+  apply_body<KIND, WD, NAG, false>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
 }
 
 __device__ __forceinline__ void advance_one(const OptArgs& a) {
@@ -398,19 +448,36 @@ static void launch_group(const OptGroup& g, dim3 grid, hipStream_t s) {
   }
 }
 
-template <bool WD, bool NAG>
+template <bool WD, bool NAG, bool EMA>
 static void launch_one(const OptArgs& a, int blocks, hipStream_t s) {
   const dim3 grid(blocks), blk(256);
   switch (a.kind) {
-    case OPT_SGD: hipLaunchKernelGGL((apply_gradients_kernel<OPT_SGD, WD, false>), grid, blk, 0, s, a); break;
-    case OPT_MOMENTUM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG>), grid, blk, 0, s, a); break;
-    case OPT_ADAM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_ADAM, WD, false>), grid, blk, 0, s, a); break;
-    default: hipLaunchKernelGGL((apply_gradients_kernel<OPT_RMSPROP, WD, false>), grid, blk, 0, s, a); break;
+    case OPT_SGD: hipLaunchKernelGGL((apply_gradients_kernel<OPT_SGD, WD, false, EMA>), grid, blk, 0, s, a); break;
+    case OPT_MOMENTUM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG, EMA>), grid, blk, 0, s, a); break;
+    case OPT_ADAM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_ADAM, WD, false, EMA>), grid, blk, 0, s, a); break;
+    default: hipLaunchKernelGGL((apply_gradients_kernel<OPT_RMSPROP, WD, false, EMA>), grid, blk, 0, s, a); break;
   }
+}
+template <bool EMA>
+static void launch_one_recipe(const OptArgs& a, int blocks, hipStream_t s) {
+  if (a.decay) a.nesterov ? launch_one<true, true, EMA>(a, blocks, s) : launch_one<true, false, EMA>(a, blocks, s);
+  else a.nesterov ? launch_one<false, true, EMA>(a, blocks, s) : launch_one<false, false, EMA>(a, blocks, s);
+}
+
+// an EMA's decay follows the optimizer's own step and every element's one update: no partial applies, no
+// second destinations of a ps reply
+static void check_ema(const OptArgs& a) {
+  if (!a.ema) return;
+  if (!(a.ema_decay >= 0.f && a.ema_decay < 1.f)) throw std::runtime_error("apply_gradients: ema_decay lies in [0, 1)");
+  if (a.ema_num_updates && !a.global_step)
+    throw std::runtime_error("apply_gradients: ema_num_updates needs a global_step");
+  if (a.skip_advance) throw std::runtime_error("apply_gradients: an EMA cannot be combined with skip_advance");
+  if (a.rep_slot) throw std::runtime_error("apply_gradients: an EMA cannot be combined with a ps reply");
 }
 
 void launch_apply_gradients_group(const OptArgs* o, int n, hipStream_t s) {
   if (n < 1 || n > OPT_GROUP_MAX) throw std::runtime_error("apply_gradients_group: 1..4 optimizers");
+  if (n == 1 && o[0].ema) return launch_apply_gradients(o[0], s);  // the group kernels have no EMA instantiation
   OptGroup g{};
   g.n = n;
   g.first[0] = 0;
@@ -420,6 +487,8 @@ void launch_apply_gradients_group(const OptArgs* o, int n, hipStream_t s) {
     check_sched(o[i]);
     if (o[i].sched && n > 1)
       throw std::runtime_error("apply_gradients_group: an optimizer with a schedule takes a launch of its own");
+    if (o[i].ema && n > 1)
+      throw std::runtime_error("apply_gradients_group: an optimizer with an EMA takes a launch of its own");
     decay = decay || o[i].decay;
     nag = nag || o[i].nesterov;
     g.o[i] = o[i];
@@ -444,9 +513,77 @@ void launch_opt_advance_reply(const OptArgs* a, int n, hipStream_t s) {
 
 void launch_apply_gradients(const OptArgs& a, hipStream_t s) {
   check_sched(a);
+  check_ema(a);
   const int blocks = apply_blocks(a);
-  if (a.decay) a.nesterov ? launch_one<true, true>(a, blocks, s) : launch_one<true, false>(a, blocks, s);
-  else a.nesterov ? launch_one<false, true>(a, blocks, s) : launch_one<false, false>(a, blocks, s);
+  if (a.ema) launch_one_recipe<true>(a, blocks, s);
+  else launch_one_recipe<false>(a, blocks, s);
+}
+
+// Exchanges the masters of a var list with their EMA shadows and rewrites the bf16 working copies from
+// the new masters, over the optimizer's own plan: flat ranges with 16-byte loads and stores, transposed
+// variables through the LDS tile as the apply lays them out (copy = f2bf(master), the apply's invariant).
+// Every element belongs to one work item and nothing is handed between workgroups: no counters, no step.
+__global__ __launch_bounds__(256) void ema_swap_kernel(OptArgs a) {
+  __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
+  for (int wi = blockIdx.x; wi < a.nwork; wi += gridDim.x) {
+    const OptWork w = a.work[wi];
+    const OptSeg sg = a.segs[w.seg];
+    if (w.kind == 0) {
+      const long base = sg.off + w.start;
+      const long n4 = ((base & 3) == 0) ? (w.count / 4) * 4 : 0;
+      for (long j = threadIdx.x * 4; j < n4; j += 256 * 4) {
+        const f32x4_t p = *reinterpret_cast<const f32x4_t*>(a.p + base + j);
+        const f32x4_t e = *reinterpret_cast<const f32x4_t*>(a.ema + base + j);
+        *reinterpret_cast<f32x4_t*>(a.p + base + j) = e;
+        *reinterpret_cast<f32x4_t*>(a.ema + base + j) = p;
+        store_copies(e, sg.w16 ? sg.w16 + w.start + j : nullptr, nullptr, nullptr);
+      }
+      for (long j = n4 + threadIdx.x; j < w.count; j += 256) {
+        const long li = w.start + j, i = sg.off + li;
+        const float p = a.p[i], e = a.ema[i];
+        a.p[i] = e;
+        a.ema[i] = p;
+        if (sg.w16) sg.w16[li] = f2bf(e);
+      }
+    } else {
+      const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+      const int c = w.c0 + tx;
+      float pv[16], ev[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int r = w.r0 + ty + 4 * u;
+        // out-of-tile lanes load the segment's first element (never stored), as in the apply
+        const bool ok = r < sg.R && c < sg.C;
+        const long i = sg.off + (ok ? ((long)r * sg.T + w.t) * sg.C + c : 0);
+        pv[u] = a.p[i];
+        ev[u] = a.ema[i];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int rr = ty + 4 * u, r = w.r0 + rr;
+        if (r < sg.R && c < sg.C) {
+          const long li = ((long)r * sg.T + w.t) * sg.C + c, i = sg.off + li;
+          a.p[i] = ev[u];
+          a.ema[i] = pv[u];
+          const bf16 b = f2bf(ev[u]);
+          if (sg.w16) sg.w16[li] = b;
+          tile[rr][tx] = b;
+        }
+      }
+      __syncthreads();
+      for (int cc = ty; cc < 64; cc += 4) {
+        const int c = w.c0 + cc, r = w.r0 + tx;
+        if (r < sg.R && c < sg.C && sg.wt16) sg.wt16[((long)c * sg.T + w.t) * sg.R + r] = tile[tx][cc];
+      }
+      __syncthreads();
+    }
+  }
+}
+
+void launch_ema_swap(const OptArgs& a, hipStream_t s) {
+  if (!a.ema) throw std::runtime_error("ema_swap: the optimizer has no EMA");
+  if (a.nwork < 1) return;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(apply_blocks(a)), dim3(256), 0, s, a);
 }
 
 }  // namespace dtfe

@@ -32,6 +32,7 @@ __all__ = [
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
     "augment_rows", "augment_draws", "AUG_SALT", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
+    "ema_swap", "ema_decay_value", "ema_update_ref",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -794,7 +795,8 @@ def gemm_group(anchor):
 
 # --------------------------------------------------------------- optimizer
 def opt_state(kind, p, segs, work, done, s1=None, s2=None, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, rho=0.0,
-              beta_pow=None, global_step=None, wd=None, sched=None, lr_out=None, nesterov=False, decay=False):
+              beta_pow=None, global_step=None, wd=None, sched=None, lr_out=None, nesterov=False, decay=False,
+              ema=None, ema_decay=0.0, ema_num_updates=False, ema_out=None):
     """An optimizer bound to the native side (torch.classes.dtfe.OptState): everything that holds for its
     life, checked once - the tensors' device, dtype and length, every segment inside ``p``, every work item
     inside its segment - with the plan packed into a device blob.  apply_gradients then takes only what varies.
@@ -804,14 +806,18 @@ def opt_state(kind, p, segs, work, done, s1=None, s2=None, beta1=0.0, beta2=0.0,
     ``sched``: the blob of lr_schedule_pack - the kernel evaluates it at ``global_step`` and uses the result
     in place of the launch's ``lr``; ``lr_out``: a device float32 scalar that receives the rate a launch used.
     ``nesterov``: TF1 ApplyMomentum's use_nesterov form (momentum only).  ``decay``: launch the kernels'
-    weight-decay instantiation (some ``wd`` is non-zero); without it ``wd`` is ignored."""
+    weight-decay instantiation (some ``wd`` is non-zero); without it ``wd`` is ignored.
+    ``ema``: the shadow buffer of an exponential moving average (float32, as long as ``p``, same offsets):
+    every launch also updates it from the values it stores, with ``ema_decay`` or - ``ema_num_updates`` -
+    ``min(ema_decay, (1 + n) / (10 + n))`` at the global step after the launch's advance (ema_decay_value);
+    ``ema_out``: a device float32 scalar that receives the decay a launch used.  ema_swap exchanges the two."""
     require()
     table = lambda t, cols: torch.as_tensor(t, dtype=torch.int64).reshape(len(t), cols)
     if wd is not None:
         wd = torch.as_tensor(wd, dtype=torch.float32)
     return torch.classes.dtfe.OptState(int(kind), p, s1, s2, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
                                        done, table(segs, 6), table(work, 7), wd, sched, lr_out, bool(nesterov),
-                                       bool(decay))
+                                       bool(decay), ema, float(ema_decay), bool(ema_num_updates), ema_out)
 
 
 @functools.lru_cache(None)
@@ -836,9 +842,40 @@ def apply_gradients(state, g, g16, gscale, lr, gs_inc, wait_done=None, wait_seen
 
 
 def apply_gradients_group(states, g, g16, gscale, lrs, gs_incs, clip_scales=None):
-    """Up to four ``opt_state`` of one kind (and none with a schedule) over disjoint var lists in ONE launch,
+    """Up to four ``opt_state`` of one kind (and none with a schedule or an EMA) over disjoint var lists in ONE launch,
     each with its own rate, step increment and (``clip_scales``: a list with None where there is none) clip scale."""
     _direct("apply_gradients_group")(states, g, g16, gscale, lrs, gs_incs, clip_scales)
+
+
+def ema_swap(state):
+    """Exchange the masters of an ``opt_state``'s var list with their EMA shadows and rewrite the bf16 working
+    copies (natural and transposed) from the new masters - one launch over the optimizer's plan; slots, step
+    and counters are untouched, and a second swap restores every buffer bit for bit.  Capturable."""
+    state.ema_swap()
+
+
+def ema_decay_value(decay, num_updates, n):
+    """The decay an apply uses, as numpy float32: the host mirror of the kernel's ema_decay_eval.  Without
+    ``num_updates`` it is ``decay``; with it, ``min(decay, (1 + n) / (10 + n))`` where ``n`` is the global step
+    AFTER the apply's advance (tf.train.ExponentialMovingAverage(decay, num_updates=global_step), run after
+    minimize).  One float32 division, IEEE-rounded on both sides: the two agree bit for bit."""
+    f = np.float32
+    d = f(decay)
+    if not num_updates:
+        return d
+    n = int(n)
+    r = f(f(1 + n) / f(10 + n))
+    return r if r < d else d
+
+
+def ema_update_ref(shadow, value, d):
+    """One EMA update of numpy float32 arrays, the host mirror of the kernel's ema_update (TF1
+    assign_moving_average): ``shadow - (shadow - value) * (1 - d)``, every operation rounded once."""
+    f = np.float32
+    shadow, value = np.asarray(shadow, dtype=f), np.asarray(value, dtype=f)
+    omd = f(f(1) - f(d))
+    with np.errstate(all="ignore"):
+        return (shadow - ((shadow - value) * omd).astype(f)).astype(f)
 
 
 # learning-rate schedules (csrc/kernels/optim.h LrSchedule / lr_schedule_eval)

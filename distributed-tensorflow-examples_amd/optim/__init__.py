@@ -10,6 +10,7 @@ exact PyTorch path with the same formulas.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from dataclasses import dataclass, field
@@ -169,6 +170,11 @@ class OptimizerConfig:
     decay_vars: tuple | None = None
     # momentum only: TF1 ApplyMomentum's use_nesterov
     nesterov: bool = False
+    # tf.train.ExponentialMovingAverage of the var list, updated inside the fused apply: 0 = off, else in
+    # [0, 1).  ema_num_updates: the decay is min(ema_decay, (1 + n) / (10 + n)) at the global step n after
+    # the apply (TF's num_updates=global_step)
+    ema_decay: float = 0.0
+    ema_num_updates: bool = False
 
     def has_schedule(self):
         return bool(self.lr_boundaries or self.lr_values or self.lr_decay_steps or self.lr_warmup_steps)
@@ -223,7 +229,10 @@ class Optimizer:
     Slot variables follow TF1 naming: ``<var>/Adam``, ``<var>/Adam_1``;
     ``<var>/RMSProp`` (initialised to ones), ``<var>/RMSProp_1``;
     ``<var>/Momentum``.  Adam's non-slot ``beta1_power``/``beta2_power`` are a
-    2-element device tensor advanced by the kernel itself.
+    2-element device tensor advanced by the kernel itself.  With ``cfg.ema_decay`` the optimizer also keeps
+    ``tf.train.ExponentialMovingAverage`` shadows of its variables (``ema``, checkpointed as
+    ``<var>/ExponentialMovingAverage``), updated by the same launch; ``swap_ema`` / ``averaged`` put them in the
+    variables' place.  On the CPU the update goes through the numpy-float32 mirror: the same bits as the kernel's.
 
     On the GPU the optimizer is bound to the native side once (``ops.opt_state``): plan, slots, counters
     and the recipe are checked and fixed at construction, and of the config only ``cfg.lr`` is read at
@@ -234,6 +243,7 @@ class Optimizer:
 
     SLOT_NAMES = {"adam": ("Adam", "Adam_1"), "rmsprop": ("RMSProp", "RMSProp_1"), "momentum": ("Momentum",),
                   "sgd": ()}
+    EMA_NAME = "ExponentialMovingAverage"
 
     def __init__(self, cfg: OptimizerConfig, params: FlatParams, var_list=None, global_step=None,
                  beta_power_names=("beta1_power", "beta2_power"), slots_of=None, beta_pow=None):
@@ -298,6 +308,56 @@ class Optimizer:
         # per variable of the var list; float32 as the kernel holds it
         self.wd = [wd if wd > 0 and n in decay_vars else 0.0 for n in self.var_list]
         self.decay = any(w != 0 for w in self.wd)
+        # exponential moving average: the shadow starts as the variables' initial values (TF initialises it
+        # so); full-size like the slots, elements outside the var list are never written
+        d = float(getattr(cfg, "ema_decay", 0.0) or 0.0)
+        if not 0.0 <= d < 1.0 or not float(ops.ema_decay_value(d, False, 0)) < 1.0:
+            raise ValueError("ema_decay must lie in [0, 1) (0 = no moving average), got %r" % (cfg.ema_decay,))
+        self.ema_decay = d
+        self.ema_num_updates = bool(getattr(cfg, "ema_num_updates", False))
+        self.ema, self._ema_out = None, None
+        if self.ema_num_updates and not d > 0:
+            raise ValueError("Optimizer: ema_num_updates needs ema_decay > 0")
+        if d > 0:
+            if self.ema_num_updates and self.global_step is None:
+                raise ValueError("Optimizer: ema_num_updates makes the decay a function of global_step - pass one")
+            self.ema = self.P.master.clone()
+            self._ema_out = torch.full((1,), float(ops.ema_decay_value(d, False, 0)), dtype=torch.float32,
+                                       device=self.device)
+
+    @property
+    def current_ema_decay(self):
+        """The decay the last step's moving average used (before any step: ema_decay) as a 1-element device
+        tensor - read it on the host only when it is wanted; None without ema_decay."""
+        return self._ema_out
+
+    def swap_ema(self):
+        """Exchange the var list's masters with their moving averages and rewrite the bf16 working copies
+        from the new masters: one launch on the GPU (capturable), tensor ops on the CPU.  A second call
+        restores masters, averages and copies bit for bit."""
+        if self.ema is None:
+            raise ValueError("Optimizer.swap_ema: the optimizer keeps no moving average (ema_decay is 0)")
+        if self.device.type == "cuda":
+            ops.ema_swap(self._state)
+            return
+        with torch.no_grad():
+            for name in self.var_list:
+                o, n = self.P.offsets[name], self.P.spec(name).numel
+                v, e = self.P.master[o:o + n], self.ema[o:o + n]
+                t = v.clone()
+                v.copy_(e)
+                e.copy_(t)
+            self.P.refresh_copies()
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside the block the model's weights (masters and bf16 copies) are the moving averages; the
+        trained ones come back on leaving it, also when the body raises."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
 
     @property
     def current_lr(self):
@@ -347,7 +407,9 @@ class Optimizer:
                                     beta1=c.beta1, beta2=c.beta2, eps=c.resolved_eps(), momentum=c.momentum,
                                     rho=c.rho, beta_pow=self.beta_pow, global_step=self.global_step,
                                     wd=self.wd if self.decay else None, sched=sched, lr_out=self._lr_out,
-                                    nesterov=self.nesterov, decay=self.decay)
+                                    nesterov=self.nesterov, decay=self.decay, ema=self.ema,
+                                    ema_decay=self.ema_decay, ema_num_updates=self.ema_num_updates,
+                                    ema_out=self._ema_out)
 
     def _wait_mask(self, names) -> int:  # the kernel's wait_segs: 32 bits of var_list indices
         idx = [self.var_list.index(n) if n in self.var_list else -1 for n in names]
@@ -394,7 +456,8 @@ class Optimizer:
         # workgroup may advance the shared global_step before another optimizer's workgroups have read
         # it, and those would evaluate their schedule one step ahead.  One launch each keeps every read
         # of the step before the launch that advances it (stream order).
-        scheduled = any(o.lr_spec is not None for o in opts)
+        # Likewise optimizers with a moving average: with num_updates its decay is a function of the step.
+        scheduled = any(o.lr_spec is not None or o.ema is not None for o in opts)
         if (len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and not scheduled
                 and all(o.device.type == "cuda" for o in opts)):
             P = opts[0].P
@@ -422,6 +485,11 @@ class Optimizer:
             b1p, b2p = self.beta_pow.tolist()
             lr_t = lr * math.sqrt(1 - b2p) / (1 - b1p)
         eps = c.resolved_eps()
+        ema_d = None
+        if self.ema is not None:  # the decay at the step after this apply's advance, as the kernel forms it
+            n = (int(self.global_step.item()) + int(gs_inc)) if self.ema_num_updates else 0
+            ema_d = ops.ema_decay_value(self.ema_decay, self.ema_num_updates, n)
+            self._ema_out[0] = float(ema_d)
         for name, wd in zip(self.var_list, self.wd):
             s = self.P.spec(name)
             o, n = self.P.offsets[name], s.numel
@@ -447,6 +515,9 @@ class Optimizer:
                 ms.mul_(c.rho).add_((1 - c.rho) * g * g)
                 mom.mul_(c.momentum).add_(lr * g / (ms + eps).sqrt())
                 v -= mom
+            if ema_d is not None:  # through the numpy mirror: the same bits as the kernel's update
+                e = self.ema[o:o + n]
+                e.copy_(torch.from_numpy(ops.ema_update_ref(e.numpy(), v.numpy(), ema_d)))
         if c.kind == "adam":
             self.beta_pow[0] *= c.beta1
             self.beta_pow[1] *= c.beta2
@@ -464,6 +535,8 @@ class Optimizer:
             for i, sn in enumerate(names):
                 buf = self.s1 if i == 0 else self.s2
                 out[f"{var}/{sn}"] = buf[o:o + n].detach().cpu().view(s.shape).clone()
+            if self.ema is not None:  # tf.train.ExponentialMovingAverage's shadow variable name
+                out[f"{var}/{self.EMA_NAME}"] = self.ema[o:o + n].detach().cpu().view(s.shape).clone()
         if self.beta_pow is not None:
             bp = self.beta_pow.detach().cpu()
             out[self.beta_power_names[0]] = bp[0].clone()
@@ -480,6 +553,12 @@ class Optimizer:
                 if key in tensors:
                     buf = self.s1 if i == 0 else self.s2
                     buf[o:o + n].copy_(tensors[key].reshape(-1).to(self.device))
+            if self.ema is not None:
+                key = f"{var}/{self.EMA_NAME}"
+                if key in tensors:
+                    self.ema[o:o + n].copy_(tensors[key].reshape(-1).to(self.device))
+                else:  # a checkpoint from a run without EMA: start the average at the restored variable
+                    self.ema[o:o + n].copy_(self.P.master[o:o + n])
         if self.beta_pow is not None and self.beta_power_names[0] in tensors:
             self.beta_pow[0] = float(tensors[self.beta_power_names[0]])
             self.beta_pow[1] = float(tensors[self.beta_power_names[1]])

@@ -19,6 +19,7 @@ import contextlib
 import json
 import os
 import sys
+import threading
 import time
 
 import numpy as np
@@ -128,6 +129,12 @@ PS_RECIPE_ERROR = ("%s: learning-rate schedules, --weight_decay and --nesterov r
                    "only - in --mode=ps the shards' optimizers own no global_step to evaluate a schedule from")
 
 
+CNN_EMA_ERROR = ("%s: the MNIST CNN's own schedule launches its Adam applies itself, in parts; pass --bucket_mb to run "
+                 "the CNN on the generic path, whose fused apply keeps the moving average")
+PS_EMA_ERROR = ("%s: the moving average of the weights runs in local and all-reduce mode only - in --mode=ps the "
+                "shards' applies write the workers' reply buffers and own no global_step")
+
+
 SPG_HOST_ERROR = ("--steps_per_graph %d: several steps per replay need --shuffle device - with --shuffle host the rows "
                   "of every batch are host indices, which cannot enter a replay")
 PS_BATCHING_ERROR = ("%s: device-side shuffling and multi-step replays run in local and all-reduce mode only - a "
@@ -201,6 +208,9 @@ def check_batching(flags, mode=None):
 def check_recipe(flags, model, mode=None):
     """The optimizer-recipe flags against mode and model, before anything is built.  (The MNIST CNN's
     own schedule is refused where that schedule is chosen, run_allreduce.)"""
+    ema = flagmod.ema_flags(flags)
+    if ema and mode == "ps":
+        raise ValueError(PS_EMA_ERROR % " ".join(ema))
     names = flagmod.recipe_flags(flags)
     if not names:
         return
@@ -228,6 +238,26 @@ def lr_metrics(opts) -> dict:
     if len(s) == 1:
         return {"lr": float(s[0].current_lr.item())}
     return {"lr_%d" % i: float(o.current_lr.item()) for i, o in enumerate(s)}
+
+
+def ema_metrics(opts) -> dict:
+    """The decay the step's moving average used, read from the device (``ema_decay``; ``ema_decay_<i>``
+    per optimizer of several).  A host read: log steps only."""
+    s = [o for o in opts if o.current_ema_decay is not None]
+    if len(s) == 1:
+        return {"ema_decay": float(s[0].current_ema_decay.item())}
+    return {"ema_decay_%d" % i: float(o.current_ema_decay.item()) for i, o in enumerate(s)}
+
+
+@contextlib.contextmanager
+def averaged_weights(opts):
+    """Inside: every optimizer's variables hold their moving averages (Optimizer.averaged); the trained
+    values come back on exit.  Optimizers without one: nothing happens."""
+    with contextlib.ExitStack() as st:
+        for o in opts:
+            if o.ema is not None:
+                st.enter_context(o.averaged())
+        yield
 
 
 def clip_metrics(clips) -> dict:
@@ -577,6 +607,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
     check_recipe(flags, model)
     check_batching(flags)
     recipe = flagmod.recipe_flags(flags)
+    ema = flagmod.ema_flags(flags)
     spg = max(1, int(getattr(flags, "steps_per_graph", 1)))
     dev_shuffle = getattr(flags, "shuffle", "host") == "device"
     prog = model.program(device, flags.batch_size, seed=flags.seed)
@@ -585,15 +616,18 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         raise ValueError(MODEL_EVAL_ERROR % (eval_every, getattr(model, "name", "")))
     # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
     # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
-    # with --clip_norm, a recipe flag or --steps_per_graph > 1, which that schedule cannot do)
+    # with --clip_norm, a recipe flag, --ema_decay or --steps_per_graph > 1, which that schedule cannot do)
     native = (hasattr(prog, "attach_data_parallel") and len(model.opt_groups) == 1
-              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe and spg == 1)))
+              and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe and not ema
+                                               and spg == 1)))
     if native and flags.clip_norm > 0:
         raise ValueError(CNN_CLIP_ERROR)
     if native and spg > 1:
         raise ValueError(CNN_SPG_ERROR % spg)
     if native and recipe:
         raise ValueError(CNN_RECIPE_ERROR % " ".join(recipe))
+    if native and ema:
+        raise ValueError(CNN_EMA_ERROR % " ".join(ema))
     gstep = torch.zeros(1, dtype=torch.int32, device=device)
     opts = []
     for i, (cfg, var_list_, bp) in enumerate(model.opt_groups):
@@ -601,11 +635,21 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         cfg.clip_norm = flags.clip_norm
         if recipe:
             apply_recipe(flags, cfg, model, var_list_)
+        if ema:
+            cfg.ema_decay, cfg.ema_num_updates = flags.ema_decay, bool(flags.ema_num_updates)
         opts.append(Optimizer(cfg, prog.P, var_list=var_list_, global_step=gstep, beta_power_names=bp))
     is_chief = rank == 0
+    # held while the variables hold their moving averages (an evaluation with --ema_decay): the checkpoint
+    # thread saves the trained values, never the swapped ones
+    weights_lock = threading.Lock()
+
+    def state_fn():
+        with weights_lock:
+            return tensors_from_flat(model, prog.P, opts, int(gstep.item())), int(gstep.item())
+
     sv = Supervisor(
         is_chief, flags.model_dir,
-        state_fn=lambda: (tensors_from_flat(model, prog.P, opts, int(gstep.item())), int(gstep.item())),
+        state_fn=state_fn,
         restore_fn=lambda t: gstep.fill_(load_flat_from_tensors(model, prog.P, opts, t)),
         init_fn=lambda: None, wait_fn=lambda: None, var_list_fn=lambda: var_list(model),
         gs_fn=lambda: int(gstep.item()),
@@ -619,7 +663,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         dist.broadcast(prog.P.master, src=0, group=group)
         dist.broadcast(gstep, src=0, group=group)
         for o in opts:
-            for b in (o.s1, o.s2, o.beta_pow):
+            for b in (o.s1, o.s2, o.beta_pow, o.ema):
                 if b is not None:
                     dist.broadcast(b, src=0, group=group)
         prog.P.refresh_copies()
@@ -659,10 +703,20 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         """One evaluation at global step ``step``: the log line, the chief's summaries, the metrics keys."""
         t_ev = time.time()
         with chief_untrained_vars(model, prog.P, world, group):
-            res = evaluator.run()
+            if ema:  # --ema_decay: the averaged weights are what is evaluated
+                with weights_lock:
+                    with averaged_weights(opts):
+                        res = evaluator.run()
+                    if device.type == "cuda":  # the trained values are back before the lock is
+                        torch.cuda.current_stream(device).synchronize()
+            else:
+                res = evaluator.run()
         row = eval_metrics_row(res, evaluator.topk, (time.time() - t_ev) * 1000)
-        log("Global step %d Test-Accuracy: %2.4f Test-Loss: %.4f" % (step, res["accuracy"], res["loss"]))
-        sv.summary(step, {k: v for k, v in row.items() if k != "test_examples"})
+        if ema:
+            row["eval_weights"] = "ema"
+        log("Global step %d Test-Accuracy%s: %2.4f Test-Loss: %.4f"
+            % (step, "(EMA)" if ema else "", res["accuracy"], res["loss"]))
+        sv.summary(step, {k: v for k, v in row.items() if k not in ("test_examples", "eval_weights")})
         return row
 
     state = {}
@@ -743,6 +797,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
                 sc.update(clip_metrics(clips))  # (the all-reduce has completed before step_all: every rank's norm)
             if recipe and log_step:
                 sc.update(lr_metrics(opts))
+            if ema and log_step:
+                sc.update(ema_metrics(opts))
             if local_step == 0 and native and ar is not None and is_chief:
                 log("schedule: " + " < ".join(prog.core.schedule))
             if log_step:
@@ -785,6 +841,14 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
             acc = prog.evaluate(torch.from_numpy(data.test.images[:test_len]).to(device),
                                 torch.from_numpy(data.test.labels[:test_len]).to(device))
             log("Test-Accuracy: %2.4f" % acc)
+            if ema:  # the same examples with the averaged weights
+                with weights_lock:
+                    with averaged_weights(opts):
+                        acc = prog.evaluate(torch.from_numpy(data.test.images[:test_len]).to(device),
+                                            torch.from_numpy(data.test.labels[:test_len]).to(device))
+                    if device.type == "cuda":
+                        torch.cuda.current_stream(device).synchronize()
+                log("EMA Test-Accuracy: %2.4f" % acc)
     finally:
         if wd is not None:
             wd.stop()

@@ -35,6 +35,11 @@ def recipe_flags(flags) -> list:
     return ["--" + n for n in names if getattr(flags, n, None)]
 
 
+def ema_flags(flags) -> list:
+    """The moving-average flags (--ema_decay, --ema_num_updates) that are set, by name."""
+    return ["--" + n for n in ("ema_decay", "ema_num_updates") if getattr(flags, n, None)]
+
+
 def add_bool(ap, name, default, help_):
     ap.add_argument("--" + name, dest=name, nargs="?", const=True, default=default, type=_bool, help=help_)
     ap.add_argument("--no" + name, dest=name, action="store_false", help=argparse.SUPPRESS)
@@ -154,6 +159,15 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "stays the cross-entropy alone, without the L2 term.  0 (default): off")
     add_bool(ap, "nesterov", False, "Nesterov momentum (TF1 MomentumOptimizer use_nesterov) for models that declare "
                                     "decaying variables (resnet20)")
+    ap.add_argument("--ema_decay", type=float, default=0.0,
+                    help="keep an exponential moving average of every trained variable "
+                         "(tf.train.ExponentialMovingAverage: shadow -= (1 - D) * (shadow - variable) after each "
+                         "update, started at the initial values), updated inside the fused apply (local / "
+                         "all-reduce modes; the MNIST CNN's own schedule needs --bucket_mb).  With it --eval_every "
+                         "and the lstm / cnn end-of-run accuracy evaluate the averaged weights, checkpoints gain "
+                         "<var>/ExponentialMovingAverage, log steps report ema_decay.  In [0, 1); 0 (default): off")
+    add_bool(ap, "ema_num_updates", False, "with --ema_decay: the decay is min(D, (1 + step) / (10 + step)) "
+                                           "(ExponentialMovingAverage's num_updates=global_step)")
     ap.add_argument("--eval_every", type=int, default=0,
                     help="evaluate on the test split whenever a multiple of N lies among the model steps an "
                          "iteration ran, and once at the end of training (local / all-reduce modes; models whose "
@@ -199,6 +213,10 @@ def parse(argv=None, model_defaults=None, prog=None):
         ap.error("--eval_examples must be >= 0 (0 = the whole test split), got %r" % args.eval_examples)
     if not args.eval_topk >= 1:
         ap.error("--eval_topk must be >= 1, got %r" % args.eval_topk)
+    if not 0 <= args.ema_decay < 1:
+        ap.error("--ema_decay must lie in [0, 1) (0 = off), got %r" % args.ema_decay)
+    if args.ema_num_updates and not args.ema_decay > 0:
+        ap.error("--ema_num_updates shapes the decay of a moving average: it needs --ema_decay")
     if args.lr_end and not args.lr_decay_steps:
         ap.error("--lr_end is the end of a linear decay: it needs --lr_decay_steps")
     return args
