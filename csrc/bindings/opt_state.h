@@ -15,12 +15,13 @@ struct OptStateObj : torch::CustomClassHolder {
   // three on the CPU.  The w16 / wt16 addresses are the caller's to keep alive (FlatParams does).
   // ema: the shadow buffer of an exponential moving average, float32 as long as p (absent: none), with its
   // decay, the num_updates form and the scalar that receives the decay a launch used (OptArgs::ema*).
+  // seg_lr: a device float32 [>= nseg] factor of the rate per segment (OptArgs::seg_lr; absent: none), momentum only.
   OptStateObj(int64_t kind, at::Tensor p, c10::optional<at::Tensor> s1, c10::optional<at::Tensor> s2, double beta1,
               double beta2, double eps, double momentum, double rho, c10::optional<at::Tensor> beta_pow,
               c10::optional<at::Tensor> global_step, at::Tensor done, const at::Tensor& segs, const at::Tensor& work,
               const c10::optional<at::Tensor>& wd, c10::optional<at::Tensor> sched, c10::optional<at::Tensor> lr_out,
               bool nesterov, bool decay, c10::optional<at::Tensor> ema, double ema_decay, bool ema_num_updates,
-              c10::optional<at::Tensor> ema_out);
+              c10::optional<at::Tensor> ema_out, c10::optional<at::Tensor> seg_lr);
 
   // every field that holds for the optimizer's life; a launch copies it and sets g / g16, gscale, lr,
   // gs_inc, wait_* and clip_scale

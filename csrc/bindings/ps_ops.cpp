@@ -399,6 +399,7 @@ void ps_service_add_group(int64_t h, const c10::intrusive_ptr<OptStateObj>& o, d
               "dtfe ps: the service applies the plain optimizers (no schedule, Nesterov or weight decay)");
   // the service writes reply destinations (w16b, wt16b, pb, rep_slot) and applies bucket by bucket
   TORCH_CHECK(!o->args.ema, "dtfe ps: the service applies the plain optimizers (no EMA)");
+  TORCH_CHECK(!o->args.seg_lr, "dtfe ps: the service applies the plain optimizers (no per-segment rate)");
   Group g{};
   g.opt = o;
   g.args = o->args;  // done_counter is set per launch (each worker channel has its own)

@@ -23,6 +23,7 @@
 #include "../kernels/head.h"
 #include "../kernels/lstm_seq.h"
 #include "../kernels/gradnorm.h"
+#include "../kernels/lars.h"
 #include "../kernels/optim.h"
 #include "opt_state.h"
 
@@ -629,7 +630,7 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
                          optional<Tensor> global_step, Tensor done, const Tensor& segs_t, const Tensor& work_t,
                          const optional<Tensor>& wd, optional<Tensor> sched, optional<Tensor> lr_out, bool nesterov,
                          bool decay, optional<Tensor> ema, double ema_decay, bool ema_num_updates,
-                         optional<Tensor> ema_out) {
+                         optional<Tensor> ema_out, optional<Tensor> seg_lr) {
   TORCH_CHECK(kind >= dtfe::OPT_SGD && kind <= dtfe::OPT_RMSPROP, "OptState: kind is 0 (sgd) .. 3 (rmsprop)");
   check_cuda(p, "p");
   TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous(), "OptState: p is contiguous float32");
@@ -689,6 +690,10 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
   };
   const Tensor S = table(segs_t, "segs", 6), W = table(work_t, "work", 7);
   const int64_t ns = S.size(0), nw = W.size(0);
+  // a factor of the rate per segment (the trust ratios of ops.layer_trust): one float for every segment
+  a.seg_lr = (const float*)bind(seg_lr, "seg_lr", is(seg_lr, at::kFloat), "float32", ns, false);
+  TORCH_CHECK(!a.seg_lr || kind == dtfe::OPT_MOMENTUM, "OptState: seg_lr (a per-segment rate) is for the momentum "
+              "optimizer, not kind ", kind);
   TORCH_CHECK(nw <= INT32_MAX, "OptState: work has too many items");
   Tensor D;
   if (wd.has_value() && wd->defined()) {
@@ -792,6 +797,71 @@ void grad_sumsq(const optional<Tensor>& g, const optional<Tensor>& g16, double g
   a.out = out.data_ptr<float>();
   a.max_blocks = (int)max_blocks;
   dtfe::launch_grad_sumsq(a, cur_stream());
+}
+
+// LARS: the norms of master and gradient of every adaptive variable and from them its trust ratio (kernels/lars.h).
+// plan: int64 [nchunk, 3] device table of (seg, offset, count <= 8192); segs: int32 [nadapt, 3] device table of
+// (seg, first chunk, chunks) - both from ops.layer_trust_plan, which checks them against the buffers; limit: the
+// largest offset + count of the plan; wd: float32 [nseg]; partials: fp32 [>= 2 nchunk]; ticket: zeroed int32 [1]
+// (the kernel resets it); sums: fp32 [nseg, 2]; trust: fp32 [nseg]; max_blocks: 0 = default grid (a test forces 1)
+void layer_trust(const Tensor& p, const optional<Tensor>& g, const optional<Tensor>& g16, double gscale,
+                 const Tensor& plan, const Tensor& segs, int64_t limit, const Tensor& wd, double eeta, double eps,
+                 const optional<Tensor>& clip_scale, const Tensor& partials, const Tensor& ticket, const Tensor& sums,
+                 const Tensor& trust, int64_t max_blocks) {
+  check_cuda(p, "p"); check_cuda(plan, "plan"); check_cuda(segs, "segs"); check_cuda(wd, "wd");
+  check_cuda(partials, "partials"); check_cuda(ticket, "ticket"); check_cuda(sums, "sums"); check_cuda(trust, "trust");
+  for (const Tensor* t : {&plan, &segs, &wd, &partials, &ticket, &sums, &trust})
+    TORCH_CHECK(t->get_device() == p.get_device(), "layer_trust: every tensor on p's device");
+  TORCH_CHECK(limit >= 0, "layer_trust: limit is >= 0");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous() && p.numel() >= limit,
+              "layer_trust: p is contiguous float32 and covers the plan (", limit, " elements)");
+  dtfe::LarsArgs a{};
+  a.p = p.data_ptr<float>();
+  if (g.has_value() && g->defined()) {
+    check_cuda(*g, "g");
+    TORCH_CHECK(g->scalar_type() == at::kFloat && g->is_contiguous() && g->numel() >= limit &&
+                    g->get_device() == p.get_device(),
+                "layer_trust: g is contiguous float32 on p's device and covers the plan (", limit, " elements)");
+    a.g = g->data_ptr<float>();
+  }
+  if (g16.has_value() && g16->defined()) {
+    check_cuda(*g16, "g16");
+    TORCH_CHECK(g16->scalar_type() == at::kBFloat16 && g16->is_contiguous() && g16->numel() >= limit &&
+                    g16->get_device() == p.get_device(),
+                "layer_trust: g16 is contiguous bfloat16 on p's device and covers the plan (", limit, " elements)");
+    a.g16 = reinterpret_cast<const dtfe::bf16*>(g16->data_ptr());
+  }
+  TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "layer_trust: exactly one of g / g16");
+  static_assert(sizeof(dtfe::LarsChunk) == 3 * sizeof(int64_t), "plan rows are LarsChunk");
+  static_assert(sizeof(dtfe::LarsSeg) == 3 * sizeof(int32_t), "segs rows are LarsSeg");
+  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 3 &&
+                  plan.size(0) <= INT32_MAX,
+              "layer_trust: plan is a contiguous int64 [nchunk, 3] table");
+  TORCH_CHECK(segs.scalar_type() == at::kInt && segs.is_contiguous() && segs.dim() == 2 && segs.size(1) == 3,
+              "layer_trust: segs is a contiguous int32 [nadapt, 3] table");
+  const int64_t nseg = wd.numel();
+  TORCH_CHECK(wd.scalar_type() == at::kFloat && wd.is_contiguous() && segs.size(0) <= nseg,
+              "layer_trust: wd is contiguous float32 [nseg], nseg at least the adaptive segments");
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.numel() >= 2 * plan.size(0),
+              "layer_trust: two float32 partials per chunk");
+  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "layer_trust: int32 ticket");
+  TORCH_CHECK(sums.scalar_type() == at::kFloat && sums.is_contiguous() && sums.numel() == 2 * nseg &&
+                  trust.scalar_type() == at::kFloat && trust.is_contiguous() && trust.numel() == nseg,
+              "layer_trust: float32 sums [nseg, 2] and trust [nseg]");
+  TORCH_CHECK(std::isfinite(eeta) && eeta > 0 && std::isfinite(eps) && eps >= 0 && max_blocks >= 0,
+              "layer_trust: eeta > 0, eps >= 0, max_blocks >= 0");
+  a.gscale = (float)gscale;
+  a.plan = reinterpret_cast<const dtfe::LarsChunk*>(plan.data_ptr()); a.nchunk = (int)plan.size(0);
+  a.segs = reinterpret_cast<const dtfe::LarsSeg*>(segs.data_ptr()); a.nadapt = (int)segs.size(0);
+  a.wd = wd.data_ptr<float>();
+  a.eeta = (float)eeta; a.eps = (float)eps;
+  a.clip_scale = clip_scale_ptr(clip_scale);
+  a.partials = partials.data_ptr<float>();
+  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
+  a.sums = sums.data_ptr<float>();
+  a.trust = trust.data_ptr<float>();
+  a.max_blocks = (int)max_blocks;
+  dtfe::launch_layer_trust(a, cur_stream());
 }
 
 // t[i] *= scale[0] over the plan's chunks (same table as grad_sumsq's)
@@ -946,7 +1016,7 @@ void opt_state_register() {
       .def(torch::init<int64_t, Tensor, optional<Tensor>, optional<Tensor>, double, double, double, double, double,
                        optional<Tensor>, optional<Tensor>, Tensor, const Tensor&, const Tensor&, const optional<Tensor>&,
                        optional<Tensor>, optional<Tensor>, bool, bool, optional<Tensor>, double, bool,
-                       optional<Tensor>>())
+                       optional<Tensor>, optional<Tensor>>())
       .def("apply", &apply_gradients)
       .def("ema_swap", &ema_swap);
 }
@@ -1681,6 +1751,9 @@ TORCH_LIBRARY(dtfe, m) {
   m.def("grad_sumsq(Tensor? g, Tensor? g16, float gscale, float clip_norm, Tensor plan, Tensor(a!) partials,"
         " Tensor(b!) ticket, Tensor(c!) out, int max_blocks=0) -> ()");
   m.def("scale_(Tensor(a!) t, Tensor scale, Tensor plan) -> ()");
+  m.def("layer_trust(Tensor p, Tensor? g, Tensor? g16, float gscale, Tensor plan, Tensor segs, int limit, Tensor wd,"
+        " float eeta, float eps, Tensor? clip_scale, Tensor(a!) partials, Tensor(b!) ticket, Tensor(c!) sums,"
+        " Tensor(d!) trust, int max_blocks=0) -> ()");
   m.def("eval_metrics(Tensor logits, Tensor labels, int k, Tensor(a!) state, Tensor(b!)? idx, Tensor(c!) ws,"
         " Tensor(d!) ticket) -> ()");
   m.def("wgrad_tallk(Tensor A, int lda, Tensor B, int ldb, int M, int N, int K, Tensor(a!) out, int ldc,"
@@ -1744,6 +1817,7 @@ TORCH_LIBRARY_IMPL(dtfe, CUDA, m) {
   m.impl("head_wgrad", &head_wgrad);
   m.impl("grad_sumsq", &grad_sumsq);
   m.impl("scale_", &scale_);
+  m.impl("layer_trust", &layer_trust);
   m.impl("eval_metrics", &eval_metrics);
   m.impl("gather_rows", &gather_rows);
   m.impl("augment_rows", &augment_rows);

@@ -113,6 +113,11 @@ struct OptArgs {
   float ema_decay;
   int ema_num_updates;
   float* ema_out;           // nullable: the last workgroup stores the decay this launch used
+  // optional per-segment factor of the rate (nullable), indexed by a work item's seg: the item's rate is
+  // lr_used * seg_lr[seg], one fp32 multiply (lr_used: the schedule's value, else lr) - the trust ratios of
+  // the launch before this one on the stream (lars.h).  OPT_MOMENTUM only.  lr_out reports lr_used.
+  // Null: the kernels' instantiation without it, and the arithmetic is exactly as before there was one
+  const float* seg_lr;
 };
 
 // the decay of a launch and one element's update (TF1 assign_moving_average), fp32 with no contraction:

@@ -184,10 +184,18 @@ __device__ constexpr int ema_unroll() {
   return 4;
 }
 
+// the rate of one segment's items under OptArgs::seg_lr
+__device__ __forceinline__ float seg_rate(float lr, float factor) {
+#pragma clang fp contract(off)
+  return lr * factor;
+}
+
 // One optimizer's share of a launch: workgroups bid = 0..nblk-1 of the grid (the whole grid for a
 // plain launch, a contiguous range of it for a grouped one).
 // lr: the launch's learning rate (launch_rate); omd: 1 - the launch's EMA decay (launch_ema_decay).
-template <int KIND, bool G16, bool WD, bool NAG, bool EMA>
+// SLR: the instantiation with a per-segment factor of the rate (OptArgs::seg_lr): an item's rate is
+// lr * seg_lr[its segment], one multiply
+template <int KIND, bool G16, bool WD, bool NAG, bool EMA, bool SLR>
 __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, float omd, int bid, int nblk,
                                             bf16 (&tile)[64][66]) {
   OptRate rt{lr, lr, omd};
@@ -199,6 +207,7 @@ __device__ __forceinline__ void apply_items(const OptArgs& a, float lr, float om
   for (int wi = bid; wi < a.nwork; wi += nblk) {
     const OptWork w = a.work[wi];
     const OptSeg sg = a.segs[w.seg];
+    if constexpr (SLR) rt.lr = rt.lr_t = seg_rate(lr, a.seg_lr[w.seg]);
     if (a.wait_done && !waited && w.seg < 32 && ((a.wait_segs >> w.seg) & 1u)) {
       // the producer (another stream, no graph edge) signals through *wait_done; poll with a bounded
       // wall-clock wait (a producer that never ran: proceed rather than hang the device)
@@ -341,14 +350,15 @@ __device__ __forceinline__ void publish_reply(const OptArgs& a) {
 // WD: the weight-decay instantiation, launched only when some segment decays (OptArgs::decay); NAG: the
 // one with the Nesterov branch (OptArgs::nesterov).  A launch with neither runs the kernel, and the
 // arithmetic, it ran before there was either.  EMA: the one that also updates the shadow buffer
-// (OptArgs::ema), launched only when there is one - the same rule
-template <int KIND, bool WD, bool NAG, bool EMA>
+// (OptArgs::ema), launched only when there is one - the same rule; SLR: the one with a per-segment rate
+// (OptArgs::seg_lr), likewise
+template <int KIND, bool WD, bool NAG, bool EMA, bool SLR>
 __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, bf16 (&tile)[64][66]) {
 #pragma clang fp contract(off)
   const float lr = launch_rate(a);
   const float d = EMA ? launch_ema_decay(a) : 0.f;
-  if (a.g) apply_items<KIND, false, WD, NAG, EMA>(a, lr, 1.f - d, bid, nblk, tile);
-  else apply_items<KIND, true, WD, NAG, EMA>(a, lr, 1.f - d, bid, nblk, tile);
+  if (a.g) apply_items<KIND, false, WD, NAG, EMA, SLR>(a, lr, 1.f - d, bid, nblk, tile);
+  else apply_items<KIND, true, WD, NAG, EMA, SLR>(a, lr, 1.f - d, bid, nblk, tile);
   // last workgroup: advance the non-slot scalars.  Every thread read them at its start and
   // used the value; after the barrier one lane takes a ticket (relaxed agent atomics - nothing
   // is handed between workgroups, so no fences) and the last arriver updates them.
@@ -376,10 +386,10 @@ __device__ __forceinline__ void apply_body(const OptArgs& a, int bid, int nblk, 
   }
 }
 
-template <int KIND, bool WD, bool NAG, bool EMA>
+template <int KIND, bool WD, bool NAG, bool EMA, bool SLR = false>
 __global__ __launch_bounds__(256) void apply_gradients_kernel(OptArgs a) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
-  apply_body<KIND, WD, NAG, EMA>(a, blockIdx.x, gridDim.x, tile);
+  apply_body<KIND, WD, NAG, EMA, SLR>(a, blockIdx.x, gridDim.x, tile);
 }
 
 // Several optimizers of one kind in ONE launch (the GAN's two Adams over disjoint var lists):
@@ -387,13 +397,14 @@ __global__ __launch_bounds__(256) void apply_gradients_kernel(OptArgs a) {
 // beta powers and global-step increment, exactly as separate launches would.
 // Not for optimizers with a schedule that share a global step: one optimizer's last workgroup may
 // advance the step before another's workgroups have read it (launch_apply_gradients_group refuses).
-// Nor, for the same reason, for optimizers with an EMA: the group kernels have no EMA instantiation.
+// Nor, for the same reason, for optimizers with an EMA: the group kernels have no EMA instantiation -
+// and none with a per-segment rate.
 template <int KIND, bool WD, bool NAG>
 __global__ __launch_bounds__(256) void apply_gradients_group_kernel(OptGroup g) {
   __shared__ __attribute__((aligned(16))) bf16 tile[64][66];
   int i = 0;
   while (i + 1 < g.n && (int)blockIdx.x >= g.first[i + 1]) ++i;
-  apply_body<KIND, WD, NAG, false>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
+  apply_body<KIND, WD, NAG, false, false>(g.o[i], blockIdx.x - g.first[i], g.first[i + 1] - g.first[i], tile);
 }
 
 __device__ __forceinline__ void advance_one(const OptArgs& a) {
@@ -433,6 +444,8 @@ static void check_sched(const OptArgs& a) {
   if (a.sched && !a.global_step) throw std::runtime_error("apply_gradients: a learning-rate schedule needs a global_step");
   if (a.nesterov && a.kind != OPT_MOMENTUM)
     throw std::runtime_error("apply_gradients: nesterov is for the momentum optimizer");
+  if (a.seg_lr && a.kind != OPT_MOMENTUM)
+    throw std::runtime_error("apply_gradients: a per-segment rate (seg_lr) is for the momentum optimizer");
 }
 
 // the instantiation of a launch: WD when some segment decays, NAG (momentum only) when some optimizer
@@ -453,7 +466,10 @@ static void launch_one(const OptArgs& a, int blocks, hipStream_t s) {
   const dim3 grid(blocks), blk(256);
   switch (a.kind) {
     case OPT_SGD: hipLaunchKernelGGL((apply_gradients_kernel<OPT_SGD, WD, false, EMA>), grid, blk, 0, s, a); break;
-    case OPT_MOMENTUM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG, EMA>), grid, blk, 0, s, a); break;
+    case OPT_MOMENTUM:
+      if (a.seg_lr) hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG, EMA, true>), grid, blk, 0, s, a);
+      else hipLaunchKernelGGL((apply_gradients_kernel<OPT_MOMENTUM, WD, NAG, EMA>), grid, blk, 0, s, a);
+      break;
     case OPT_ADAM: hipLaunchKernelGGL((apply_gradients_kernel<OPT_ADAM, WD, false, EMA>), grid, blk, 0, s, a); break;
     default: hipLaunchKernelGGL((apply_gradients_kernel<OPT_RMSPROP, WD, false, EMA>), grid, blk, 0, s, a); break;
   }
@@ -477,7 +493,8 @@ static void check_ema(const OptArgs& a) {
 
 void launch_apply_gradients_group(const OptArgs* o, int n, hipStream_t s) {
   if (n < 1 || n > OPT_GROUP_MAX) throw std::runtime_error("apply_gradients_group: 1..4 optimizers");
-  if (n == 1 && o[0].ema) return launch_apply_gradients(o[0], s);  // the group kernels have no EMA instantiation
+  // the group kernels have no EMA instantiation and none with a per-segment rate
+  if (n == 1 && (o[0].ema || o[0].seg_lr)) return launch_apply_gradients(o[0], s);
   OptGroup g{};
   g.n = n;
   g.first[0] = 0;
@@ -489,6 +506,8 @@ void launch_apply_gradients_group(const OptArgs* o, int n, hipStream_t s) {
       throw std::runtime_error("apply_gradients_group: an optimizer with a schedule takes a launch of its own");
     if (o[i].ema && n > 1)
       throw std::runtime_error("apply_gradients_group: an optimizer with an EMA takes a launch of its own");
+    if (o[i].seg_lr && n > 1)
+      throw std::runtime_error("apply_gradients_group: an optimizer with a per-segment rate takes a launch of its own");
     decay = decay || o[i].decay;
     nag = nag || o[i].nesterov;
     g.o[i] = o[i];

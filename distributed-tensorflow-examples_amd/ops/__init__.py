@@ -33,6 +33,7 @@ __all__ = [
     "augment_rows", "augment_draws", "AUG_SALT", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
     "ema_swap", "ema_decay_value", "ema_update_ref",
+    "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -796,7 +797,7 @@ def gemm_group(anchor):
 # --------------------------------------------------------------- optimizer
 def opt_state(kind, p, segs, work, done, s1=None, s2=None, beta1=0.0, beta2=0.0, eps=0.0, momentum=0.0, rho=0.0,
               beta_pow=None, global_step=None, wd=None, sched=None, lr_out=None, nesterov=False, decay=False,
-              ema=None, ema_decay=0.0, ema_num_updates=False, ema_out=None):
+              ema=None, ema_decay=0.0, ema_num_updates=False, ema_out=None, seg_lr=None):
     """An optimizer bound to the native side (torch.classes.dtfe.OptState): everything that holds for its
     life, checked once - the tensors' device, dtype and length, every segment inside ``p``, every work item
     inside its segment - with the plan packed into a device blob.  apply_gradients then takes only what varies.
@@ -810,14 +811,16 @@ def opt_state(kind, p, segs, work, done, s1=None, s2=None, beta1=0.0, beta2=0.0,
     ``ema``: the shadow buffer of an exponential moving average (float32, as long as ``p``, same offsets):
     every launch also updates it from the values it stores, with ``ema_decay`` or - ``ema_num_updates`` -
     ``min(ema_decay, (1 + n) / (10 + n))`` at the global step after the launch's advance (ema_decay_value);
-    ``ema_out``: a device float32 scalar that receives the decay a launch used.  ema_swap exchanges the two."""
+    ``ema_out``: a device float32 scalar that receives the decay a launch used.  ema_swap exchanges the two.
+    ``seg_lr``: a device float32 vector, one factor per segment (momentum only): a launch's rate for a segment's
+    elements is its rate times ``seg_lr[seg]`` as it stands when the launch runs (layer_trust's ``trust``)."""
     require()
     table = lambda t, cols: torch.as_tensor(t, dtype=torch.int64).reshape(len(t), cols)
     if wd is not None:
         wd = torch.as_tensor(wd, dtype=torch.float32)
     return torch.classes.dtfe.OptState(int(kind), p, s1, s2, beta1, beta2, eps, momentum, rho, beta_pow, global_step,
                                        done, table(segs, 6), table(work, 7), wd, sched, lr_out, bool(nesterov),
-                                       bool(decay), ema, float(ema_decay), bool(ema_num_updates), ema_out)
+                                       bool(decay), ema, float(ema_decay), bool(ema_num_updates), ema_out, seg_lr)
 
 
 @functools.lru_cache(None)
@@ -988,6 +991,83 @@ def scale_(t, scale, plan):
         return
     for o, n in plan.tolist():
         t[o:o + n] *= scale[0]
+
+
+LARS_CHUNK_MAX = 8192  # csrc/kernels/lars.h
+
+
+def layer_trust_plan(segs, master, chunk=0):
+    """The tables of a layer_trust launch.  ``segs`` = [(seg, offset, numel)] of the adaptive variables in the
+    flat buffer of ``master`` (seg: the variable's index in the optimizer's var list), cut into chunks of at
+    most ``chunk`` elements (0: LARS_CHUNK_MAX; a multiple of 1024 up to it).  The largest chunk is the
+    measured choice at both ends (profiles/lars_apply.txt): ResNet-20's 0.27 M elements make only 35 workgroups
+    of it, yet 2048- and 1024-element chunks - 4 and 8 times the workgroups - ran 1.1 and 1.4 times as long,
+    every further workgroup costing a ticket and a partial more than its share of the read saves; at
+    ResNet-50's 25.5 M they ran 2.0 and 3.4 times as long.
+    The chunks cover exactly those elements: no padding, no other variable.  Returns (plan, ranges, limit):
+    plan int64 [nchunk, 3] rows (seg, offset, count), ranges int32 [nadapt, 3] rows (seg, first chunk,
+    chunks) - both on master's device - and limit, the end of the last element the plan reads."""
+    if not chunk:
+        chunk = LARS_CHUNK_MAX
+    if chunk < 1024 or chunk > LARS_CHUNK_MAX or chunk % 1024:
+        raise ValueError("layer_trust_plan: chunk is a multiple of 1024 up to %d, got %r" % (LARS_CHUNK_MAX, chunk))
+    rows, ranges, limit, seen = [], [], 0, set()
+    for seg, off, n in segs:
+        seg, off, n = int(seg), int(off), int(n)
+        if off < 0 or n < 1 or off + n > master.numel():
+            raise ValueError("layer_trust_plan: segment (%d, %d) outside a buffer of %d" % (off, n, master.numel()))
+        if seg < 0 or seg >= 2 ** 31 or seg in seen:
+            raise ValueError("layer_trust_plan: segment index %d is negative or listed twice" % seg)
+        seen.add(seg)
+        first = len(rows)
+        rows += [[seg, off + st, min(chunk, n - st)] for st in range(0, n, chunk)]
+        ranges.append([seg, first, len(rows) - first])
+        limit = max(limit, off + n)
+    if len(rows) >= 2 ** 31:
+        raise ValueError("layer_trust_plan: too many chunks")
+    return (torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(master.device),
+            torch.tensor(ranges, dtype=torch.int32).reshape(-1, 3).to(master.device), limit)
+
+
+def lars_trust_ref(sum_w, sum_g, eeta, wd, eps, clip_scale=None):
+    """The trust ratio of one variable as numpy float32 from its two sums of squares: the host mirror of the
+    kernel's lars_trust_eval (tf.contrib.opt.LARSOptimizer.compute_lr), operation for operation -
+    ``eeta * |w| / (|g| + wd * |w| + eps)`` when both norms are positive, else 1; ``clip_scale`` (a global-norm
+    clip's factor) multiplies ``|g|`` first.  One IEEE square root per norm and one IEEE division, every
+    other operation rounded once: the two agree bit for bit."""
+    f = np.float32
+    with np.errstate(all="ignore"):
+        wn, gn = np.sqrt(f(sum_w)), np.sqrt(f(sum_g))
+        if clip_scale is not None:
+            gn = f(gn * f(clip_scale))
+        if not (wn > 0 and gn > 0):
+            return f(1)
+        return f(f(f(eeta) * wn) / f(f(gn + f(f(wd) * wn)) + f(eps)))
+
+
+def layer_trust(p, g, g16, gscale, plan, ranges, limit, wd, eeta, eps, clip_scale, partials, ticket, sums, trust,
+                max_blocks=0):
+    """LARS: for every adaptive variable (``plan`` / ``ranges`` / ``limit``: layer_trust_plan) ``sums[seg]`` =
+    (sum of p^2 over the fp32 master, sum of (gscale * g)^2) and ``trust[seg]`` = lars_trust_ref of the two
+    with ``wd[seg]``; the other entries of ``sums`` and ``trust`` are not written.  Exactly one of ``g``
+    (fp32) / ``g16`` (bf16).  GPU: one launch, bitwise reproducible whatever the grid (``max_blocks`` caps it,
+    for tests); ``partials`` (fp32, two per chunk) and ``ticket`` (zeroed int32) are its scratch.  CPU: float32
+    sums, the same mirror."""
+    if p.is_cuda:
+        require().layer_trust(p, g, g16, gscale, plan, ranges, limit, wd, eeta, eps, clip_scale, partials, ticket,
+                              sums, trust, max_blocks)
+        return
+    f = np.float32
+    x = g if g is not None else g16.float()
+    rows = plan.tolist()
+    clip = None if clip_scale is None else float(clip_scale[0])
+    for seg, first, n in ranges.tolist():
+        idx = torch.cat([torch.arange(o, o + c) for _s, o, c in rows[first:first + n]])
+        sw = (p[idx] * p[idx]).sum(dtype=torch.float32)
+        gs = x[idx] * float(f(gscale))
+        sg = (gs * gs).sum(dtype=torch.float32)
+        sums.view(-1)[2 * seg], sums.view(-1)[2 * seg + 1] = float(sw), float(sg)
+        trust[seg] = float(lars_trust_ref(f(sw), f(sg), eeta, f(wd[seg]), eps, clip))
 
 
 # the words of an evaluation state (csrc/kernels/eval.h EvalState): int64, the last one a float64's bits

@@ -15,6 +15,7 @@ import math
 import os
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -175,6 +176,13 @@ class OptimizerConfig:
     # the apply (TF's num_updates=global_step)
     ema_decay: float = 0.0
     ema_num_updates: bool = False
+    # momentum only: layer-wise adaptive rate scaling (tf.contrib.opt.LARSOptimizer).  lars_eeta > 0 turns it
+    # on: every variable of lars_vars (None: the whole var list) takes the rate times its trust ratio
+    # lars_eeta * |w| / (|g| + wd * |w| + lars_epsilon), wd being that variable's weight decay; the other
+    # variables of the var list (the skip list: BatchNorm, biases) keep the rate
+    lars_eeta: float = 0.0
+    lars_epsilon: float = 0.0
+    lars_vars: tuple | None = None
 
     def has_schedule(self):
         return bool(self.lr_boundaries or self.lr_values or self.lr_decay_steps or self.lr_warmup_steps)
@@ -221,6 +229,52 @@ class GlobalNormClip:
     @property
     def norm(self):
         return self.out[:1]
+
+
+class LayerTrust:
+    """The trust ratios of LARS (``tf.contrib.opt.LARSOptimizer``) over a var list of a FlatParams, on the
+    device: ``compute`` launches the norms of master and ``gscale * grad`` of every adaptive variable into
+    ``sums[i] = (sum w^2, sum g^2)`` and ``trust[i] = eeta * |w| / (|g| + wd[i] * |w| + eps)`` (1 where a norm is
+    zero), ``i`` the variable's index in the var list.  The variables outside ``adaptive`` hold a trust of
+    exactly 1, written here once.  An ``Optimizer`` with ``lars_eeta`` owns one and binds ``trust`` into its
+    fused apply as the per-segment factor of the rate.  Stateless: nothing to checkpoint."""
+
+    def __init__(self, params: FlatParams, var_list, adaptive, wd, eeta: float, eps: float = 0.0, chunk: int = 0):
+        if not (eeta > 0 and math.isfinite(eeta)) or not (eps >= 0 and math.isfinite(eps)):
+            raise ValueError("LayerTrust: eeta must be > 0 and epsilon >= 0, got %r and %r" % (eeta, eps))
+        var_list = list(var_list)
+        unknown = [n for n in adaptive if n not in var_list]
+        if unknown:
+            raise ValueError("LayerTrust: the adaptive variables %r are not in the var list" % (unknown,))
+        if len(wd) != len(var_list):
+            raise ValueError("LayerTrust: one weight decay per variable of the var list")
+        self.P = params
+        self.eeta, self.eps = float(eeta), float(eps)
+        self.adaptive = [n for n in var_list if n in set(adaptive)]
+        self.index = [var_list.index(n) for n in self.adaptive]
+        dev, nseg = params.device, len(var_list)
+        self.plan, self.ranges, self.limit = ops.layer_trust_plan(
+            [(i, params.offsets[n], params.spec(n).numel) for i, n in zip(self.index, self.adaptive)], params.master,
+            chunk)
+        self.wd = torch.tensor([float(w) for w in wd], dtype=torch.float32).reshape(nseg).to(dev)
+        self.partials = torch.zeros(max(1, 2 * self.plan.shape[0]), dtype=torch.float32, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sums = torch.zeros(nseg, 2, dtype=torch.float32, device=dev)
+        self.trust = torch.ones(nseg, dtype=torch.float32, device=dev)
+        self.launches = 0  # how often compute ran (tests: an optimizer without LARS never launches)
+
+    def compute(self, grad=None, grad16=None, gscale: float = 1.0, clip_scale=None, max_blocks: int = 0):
+        """Launch on the current stream; returns ``trust``.  ``clip_scale``: the 1-element device tensor of a
+        global-norm clip computed before (the clip scales the gradient the optimizer sees).
+        (``max_blocks``: test hook, caps the grid.)"""
+        if grad is None and grad16 is None:
+            grad = self.P.grad
+        if (grad if grad is not None else grad16).numel() < self.P.total:
+            raise ValueError("LayerTrust: the gradient is shorter than the flat parameter buffer")
+        self.launches += 1
+        ops.layer_trust(self.P.master, grad, grad16, gscale, self.plan, self.ranges, self.limit, self.wd, self.eeta,
+                        self.eps, clip_scale, self.partials, self.ticket, self.sums, self.trust, max_blocks)
+        return self.trust
 
 
 class Optimizer:
@@ -324,6 +378,29 @@ class Optimizer:
             self.ema = self.P.master.clone()
             self._ema_out = torch.full((1,), float(ops.ema_decay_value(d, False, 0)), dtype=torch.float32,
                                        device=self.device)
+        # LARS: a trust ratio per variable, computed by a launch of its own before the apply, which reads it
+        # as the per-segment factor of the rate.  No state to save.
+        eeta = float(getattr(cfg, "lars_eeta", 0.0) or 0.0)
+        self.lars = None
+        if eeta < 0:
+            raise ValueError("lars_eeta must be >= 0 (0 = no layer-wise scaling), got %r" % (cfg.lars_eeta,))
+        if eeta > 0:
+            if cfg.kind != "momentum":
+                raise ValueError("Optimizer: lars_eeta is an option of the momentum optimizer, not of %r" % (cfg.kind,))
+            lars_vars = getattr(cfg, "lars_vars", None)
+            lars_vars = self.var_list if lars_vars is None else list(lars_vars)
+            unknown = [n for n in lars_vars if n not in self.var_list]
+            if unknown:
+                raise ValueError("Optimizer: lars_vars %r are not in the var list" % (unknown,))
+            self.lars = LayerTrust(self.P, self.var_list, lars_vars, self.wd, eeta,
+                                   float(getattr(cfg, "lars_epsilon", 0.0) or 0.0))
+
+    @property
+    def layer_trust(self):
+        """The last step's trust ratio of every variable of the var list ([nseg] device tensor, 1 for the
+        variables LARS skips; before any step: all 1) - read it on the host only when it is wanted; None
+        without lars_eeta."""
+        return None if self.lars is None else self.lars.trust
 
     @property
     def current_ema_decay(self):
@@ -409,7 +486,7 @@ class Optimizer:
                                     wd=self.wd if self.decay else None, sched=sched, lr_out=self._lr_out,
                                     nesterov=self.nesterov, decay=self.decay, ema=self.ema,
                                     ema_decay=self.ema_decay, ema_num_updates=self.ema_num_updates,
-                                    ema_out=self._ema_out)
+                                    ema_out=self._ema_out, seg_lr=self.layer_trust)
 
     def _wait_mask(self, names) -> int:  # the kernel's wait_segs: 32 bits of var_list indices
         idx = [self.var_list.index(n) if n in self.var_list else -1 for n in names]
@@ -438,8 +515,13 @@ class Optimizer:
         if self.clip_norm > 0 and wait is not None:
             # the norm needs every gradient of the var list before the first update
             raise ValueError("Optimizer.step: clip_norm cannot be combined with wait= (a gradient still in flight)")
+        if self.lars is not None and wait is not None:
+            # the norms need every gradient of the var list before the first update
+            raise ValueError("Optimizer.step: lars_eeta cannot be combined with wait= (a gradient still in flight)")
         wait = (None, None, 0) if wait is None else (wait[0], wait[1], self._wait_mask(wait[2]))
         clip = self.clip.compute(grad, grad16, gscale) if self.clip is not None else None
+        if self.lars is not None:  # after the clip, whose scale it reads; the apply reads its trust ratios
+            self.lars.compute(grad, grad16, gscale, clip_scale=clip)
         if self.device.type == "cuda":
             ops.apply_gradients(self._state, grad, grad16, gscale, self.cfg.lr, gs_inc, *wait, clip_scale=clip)
             return
@@ -457,7 +539,8 @@ class Optimizer:
         # it, and those would evaluate their schedule one step ahead.  One launch each keeps every read
         # of the step before the launch that advances it (stream order).
         # Likewise optimizers with a moving average: with num_updates its decay is a function of the step.
-        scheduled = any(o.lr_spec is not None or o.ema is not None for o in opts)
+        # And optimizers with LARS: the grouped kernels have no instantiation with a per-segment rate.
+        scheduled = any(o.lr_spec is not None or o.ema is not None or o.lars is not None for o in opts)
         if (len(opts) > 1 and len(opts) <= 4 and len(kinds) == 1 and not scheduled
                 and all(o.device.type == "cuda" for o in opts)):
             P = opts[0].P
@@ -490,9 +573,12 @@ class Optimizer:
             n = (int(self.global_step.item()) + int(gs_inc)) if self.ema_num_updates else 0
             ema_d = ops.ema_decay_value(self.ema_decay, self.ema_num_updates, n)
             self._ema_out[0] = float(ema_d)
-        for name, wd in zip(self.var_list, self.wd):
+        lr0, f = lr, np.float32
+        for i, (name, wd) in enumerate(zip(self.var_list, self.wd)):
             s = self.P.spec(name)
             o, n = self.P.offsets[name], s.numel
+            if self.lars is not None:  # the rate of this variable: one float32 multiply, as the kernel forms it
+                lr = float(f(lr0) * f(self.lars.trust[i].item()))
             v, g = self.P.master[o:o + n], grad[o:o + n] * gscale
             if wd:  # coupled L2, after the clip scale
                 g = g + wd * v

@@ -135,6 +135,15 @@ PS_EMA_ERROR = ("%s: the moving average of the weights runs in local and all-red
                 "shards' applies write the workers' reply buffers and own no global_step")
 
 
+CNN_LARS_ERROR = ("%s: the MNIST CNN's own schedule launches its Adam applies itself, in parts, before every gradient of "
+                  "the step exists; pass --bucket_mb to run the CNN on the generic path, whose optimizer forms the "
+                  "per-variable norms before its fused apply")
+PS_LARS_ERROR = ("%s: layer-wise rate scaling runs in local and all-reduce mode only - in --mode=ps the shards apply a "
+                 "push bucket by bucket and never hold a whole variable's gradient beside its weights")
+MODEL_LARS_ERROR = ("%s: only a momentum model that declares its decaying variables takes layer-wise rate scaling "
+                    "(resnet20: the conv and dense kernels are scaled, batch-norm variables and biases are not), not %r")
+
+
 SPG_HOST_ERROR = ("--steps_per_graph %d: several steps per replay need --shuffle device - with --shuffle host the rows "
                   "of every batch are host indices, which cannot enter a replay")
 PS_BATCHING_ERROR = ("%s: device-side shuffling and multi-step replays run in local and all-reduce mode only - a "
@@ -207,10 +216,14 @@ def check_batching(flags, mode=None):
 
 def check_recipe(flags, model, mode=None):
     """The optimizer-recipe flags against mode and model, before anything is built.  (The MNIST CNN's
-    own schedule is refused where that schedule is chosen, run_allreduce.)"""
+    own schedule is refused where that schedule is chosen, run_allreduce - and after it, there, a model
+    that cannot take --lars_eeta.)"""
     ema = flagmod.ema_flags(flags)
     if ema and mode == "ps":
         raise ValueError(PS_EMA_ERROR % " ".join(ema))
+    lars = flagmod.lars_flags(flags)
+    if lars and mode == "ps":
+        raise ValueError(PS_LARS_ERROR % " ".join(lars))
     names = flagmod.recipe_flags(flags)
     if not names:
         return
@@ -229,6 +242,23 @@ def apply_recipe(flags, cfg, model, var_list_):
     if getattr(model, "decay_vars", None) is not None:
         cfg.weight_decay, cfg.nesterov = flags.weight_decay, bool(flags.nesterov)
         cfg.decay_vars = tuple(n for n in model.decay_vars if n in var_list_)
+
+
+def apply_lars(flags, cfg, model, var_list_):
+    """--lars_eeta / --lars_epsilon into the OptimizerConfig of one var list: the adaptive variables are the
+    model's decaying ones, whose weight decay (--weight_decay, or none) enters the trust ratio."""
+    cfg.lars_eeta, cfg.lars_epsilon = flags.lars_eeta, flags.lars_epsilon
+    cfg.lars_vars = tuple(n for n in model.decay_vars if n in var_list_)
+
+
+def trust_metrics(opts) -> dict:
+    """The smallest and largest trust ratio of the step over the adaptive variables (``trust_min``,
+    ``trust_max``), read from the device.  A host read: log steps only."""
+    t = [o.layer_trust.cpu()[o.lars.index] for o in opts if o.lars is not None and o.lars.index]
+    if not t:
+        return {}
+    t = torch.cat(t)
+    return {"trust_min": float(t.min()), "trust_max": float(t.max())}
 
 
 def lr_metrics(opts) -> dict:
@@ -608,6 +638,7 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
     check_batching(flags)
     recipe = flagmod.recipe_flags(flags)
     ema = flagmod.ema_flags(flags)
+    lars = flagmod.lars_flags(flags)
     spg = max(1, int(getattr(flags, "steps_per_graph", 1)))
     dev_shuffle = getattr(flags, "shuffle", "host") == "device"
     prog = model.program(device, flags.batch_size, seed=flags.seed)
@@ -616,10 +647,10 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         raise ValueError(MODEL_EVAL_ERROR % (eval_every, getattr(model, "name", "")))
     # programs with their own data-parallel schedule (the MNIST CNN: the one bench.py times) run it
     # here too, unless --bucket_mb asks for generic flat-buffer buckets (a single process: only together
-    # with --clip_norm, a recipe flag, --ema_decay or --steps_per_graph > 1, which that schedule cannot do)
+    # with --clip_norm, a recipe flag, --ema_decay, --lars_eeta or --steps_per_graph > 1, which that schedule cannot do)
     native = (hasattr(prog, "attach_data_parallel") and len(model.opt_groups) == 1
               and (flags.bucket_mb is None or (world == 1 and not flags.clip_norm > 0 and not recipe and not ema
-                                               and spg == 1)))
+                                               and not lars and spg == 1)))
     if native and flags.clip_norm > 0:
         raise ValueError(CNN_CLIP_ERROR)
     if native and spg > 1:
@@ -628,6 +659,11 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         raise ValueError(CNN_RECIPE_ERROR % " ".join(recipe))
     if native and ema:
         raise ValueError(CNN_EMA_ERROR % " ".join(ema))
+    if native and lars:
+        raise ValueError(CNN_LARS_ERROR % " ".join(lars))
+    if lars and (getattr(model, "decay_vars", None) is None
+                 or any(cfg.kind != "momentum" for cfg, _vl, _bp in model.opt_groups)):
+        raise ValueError(MODEL_LARS_ERROR % (" ".join(lars), getattr(model, "name", "")))
     gstep = torch.zeros(1, dtype=torch.int32, device=device)
     opts = []
     for i, (cfg, var_list_, bp) in enumerate(model.opt_groups):
@@ -637,6 +673,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
             apply_recipe(flags, cfg, model, var_list_)
         if ema:
             cfg.ema_decay, cfg.ema_num_updates = flags.ema_decay, bool(flags.ema_num_updates)
+        if lars:
+            apply_lars(flags, cfg, model, var_list_)
         opts.append(Optimizer(cfg, prog.P, var_list=var_list_, global_step=gstep, beta_power_names=bp))
     is_chief = rank == 0
     # held while the variables hold their moving averages (an evaluation with --ema_decay): the checkpoint
@@ -799,6 +837,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
                 sc.update(lr_metrics(opts))
             if ema and log_step:
                 sc.update(ema_metrics(opts))
+            if lars and log_step:
+                sc.update(trust_metrics(opts))
             if local_step == 0 and native and ar is not None and is_chief:
                 log("schedule: " + " < ".join(prog.core.schedule))
             if log_step:

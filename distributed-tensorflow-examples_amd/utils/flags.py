@@ -40,6 +40,11 @@ def ema_flags(flags) -> list:
     return ["--" + n for n in ("ema_decay", "ema_num_updates") if getattr(flags, n, None)]
 
 
+def lars_flags(flags) -> list:
+    """The layer-wise scaling flags (--lars_eeta, --lars_epsilon) that are set, by name."""
+    return ["--" + n for n in ("lars_eeta", "lars_epsilon") if getattr(flags, n, None)]
+
+
 def add_bool(ap, name, default, help_):
     ap.add_argument("--" + name, dest=name, nargs="?", const=True, default=default, type=_bool, help=help_)
     ap.add_argument("--no" + name, dest=name, action="store_false", help=argparse.SUPPRESS)
@@ -168,6 +173,16 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "<var>/ExponentialMovingAverage, log steps report ema_decay.  In [0, 1); 0 (default): off")
     add_bool(ap, "ema_num_updates", False, "with --ema_decay: the decay is min(D, (1 + step) / (10 + step)) "
                                            "(ExponentialMovingAverage's num_updates=global_step)")
+    ap.add_argument("--lars_eeta", type=float, default=0.0,
+                    help="layer-wise adaptive rate scaling (tf.contrib.opt.LARSOptimizer) for momentum models that "
+                         "declare decaying variables (resnet20): each of those variables (conv and dense kernels) "
+                         "takes the rate times E * |w| / (|g| + D * |w| + --lars_epsilon), D being --weight_decay "
+                         "and |g| the norm after --clip_norm's scale; batch-norm scales, offsets and biases keep "
+                         "the rate.  The ratios come from one extra launch before the fused apply (local / "
+                         "all-reduce modes; the MNIST CNN's own schedule needs --bucket_mb); log steps report "
+                         "trust_min and trust_max.  0 (default): off")
+    ap.add_argument("--lars_epsilon", type=float, default=0.0,
+                    help="with --lars_eeta: the epsilon added to the trust ratio's denominator (default 0)")
     ap.add_argument("--eval_every", type=int, default=0,
                     help="evaluate on the test split whenever a multiple of N lies among the model steps an "
                          "iteration ran, and once at the end of training (local / all-reduce modes; models whose "
@@ -217,6 +232,12 @@ def parse(argv=None, model_defaults=None, prog=None):
         ap.error("--ema_decay must lie in [0, 1) (0 = off), got %r" % args.ema_decay)
     if args.ema_num_updates and not args.ema_decay > 0:
         ap.error("--ema_num_updates shapes the decay of a moving average: it needs --ema_decay")
+    if not (args.lars_eeta >= 0 and args.lars_eeta < float("inf")):
+        ap.error("--lars_eeta must be >= 0 (0 = off), got %r" % args.lars_eeta)
+    if not (args.lars_epsilon >= 0 and args.lars_epsilon < float("inf")):
+        ap.error("--lars_epsilon must be >= 0, got %r" % args.lars_epsilon)
+    if args.lars_epsilon and not args.lars_eeta > 0:
+        ap.error("--lars_epsilon belongs to the trust ratio: it needs --lars_eeta")
     if args.lr_end and not args.lr_decay_steps:
         ap.error("--lr_end is the end of a linear decay: it needs --lr_decay_steps")
     return args
