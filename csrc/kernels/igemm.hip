@@ -998,8 +998,12 @@ bool run_igemm(IgemmArgs& a, hipStream_t s, float* bn_stats = nullptr) {
   Tile t = pick_tile(Mmax, a.N, a.nphase);
   a.splits = 1;
   a.ws = nullptr;
-  if (a.nphase == 1 && a.ostr == 1) {
-    // split-K when even the smallest tile leaves CUs idle and the k-loop is long
+  if (a.nphase == 1 && a.ostr == 1 && !a.acc_src) {
+    // split-K when even the smallest tile leaves CUs idle and the k-loop is long.  Never with a masked
+    // accumulation source (acc_src): the combine kernel adds out's old contents, it knows nothing of
+    // acc_src / acc_mask, and the contract is that out is not read - such a launch stays unsplit,
+    // DTFE_IG_SPLIT or not, and the tile epilogue adds src * bit.  (The ResNet-50 step's acc_src convs
+    // are 1x1 reduces of at most 8 k-tiles, below the 12 the heuristic needs: it never split them.)
     const long blocks = ((Mmax + t.bm - 1) / t.bm) * (a.N / t.bn);
     const int nk = a.ph[0].ntaps * (a.SC / IG_BK);
     int sp = env_int("DTFE_IG_SPLIT", 0);
