@@ -3,6 +3,10 @@
 // Every op writes into caller-provided (pre-allocated) tensors and launches on
 // the current HIP stream, so a whole training step built from these ops can be
 // captured into a hipGraph (torch.cuda.CUDAGraph) with zero allocations.
+//
+// The kernels trust their pointers completely, so every tensor argument of every op goes through
+// one TensorArgs (tensor_args.h): device, dtype and extent are checked before a pointer leaves it,
+// and the extent is what the kernel reads or writes.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
 #include <torch/custom_class.h>
@@ -26,28 +30,17 @@
 #include "../kernels/lars.h"
 #include "../kernels/optim.h"
 #include "opt_state.h"
+#include "tensor_args.h"
 
 using at::Tensor;
 using c10::optional;
+using dtfe::at_least;
+using dtfe::exactly;
+using dtfe::has;
+using dtfe::spans;
+using dtfe::TensorArgs;
 
 namespace {
-
-hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
-
-template <typename T>
-T* ptr_or_null(const optional<Tensor>& t) {
-  return (t.has_value() && t->defined()) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
-}
-
-void check_cuda(const Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), "dtfe: tensor '", name, "' must be on the GPU (HIP) device");
-}
-
-int dtype_code(const Tensor& t) {
-  if (t.scalar_type() == at::kBFloat16) return 0;
-  if (t.scalar_type() == at::kFloat) return 1;
-  TORCH_CHECK(false, "dtfe: unsupported dtype ", t.scalar_type());
-}
 
 // ------------------------------------------------------------------- gemm
 // torch.classes.dtfe.GemmGroup: the pieces of one grouped launch (gemm_dense.h), added by gemm /
@@ -58,7 +51,7 @@ struct GemmGroupObj : torch::CustomClassHolder {
   std::vector<Tensor> held;
   int dev = -1;  // device index of the pieces
   void hold(const Tensor& t) { held.push_back(t); }
-  void hold(const optional<Tensor>& t) { if (t.has_value() && t->defined()) held.push_back(*t); }
+  void hold(const optional<Tensor>& t) { if (has(t)) held.push_back(*t); }
   // a piece on the device of tensor `on`: add(g) records it (false: it does not fit, the caller launches it now)
   template <typename F, typename... T>
   bool join(F&& add, const Tensor& on, const T&... rest) {
@@ -70,8 +63,11 @@ struct GemmGroupObj : torch::CustomClassHolder {
     return true;
   }
   void clear() { g = dtfe::GemmGroup(); held.clear(); dev = -1; }
-  void launch() {  // on the current stream of the pieces' device; an empty group does nothing
-    if (g.pieces()) dtfe::launch_gemm_group(g, at::hip::getCurrentHIPStream(dev).stream());
+  void launch() {  // on the pieces' device (made current) and its current stream; an empty group does nothing
+    if (g.pieces()) {
+      const c10::DeviceGuard guard(c10::Device(c10::kCUDA, (c10::DeviceIndex)dev));
+      dtfe::launch_gemm_group(g, at::hip::getCurrentHIPStream(dev).stream());
+    }
     clear();
   }
   int64_t pieces() const { return g.pieces(); }
@@ -86,18 +82,25 @@ void gemm(const Tensor& A, int64_t amode, int64_t lda, const Tensor& B, int64_t 
           int64_t PH, int64_t PW, int64_t PC, const optional<Tensor>& out2, int64_t ldc2, bool out2_trans,
           const optional<Tensor>& bias_out, const optional<Tensor>& ws, const optional<Tensor>& tile_ctr,
           int64_t a_ones_row, const optional<Tensor>& ones, const GroupArg& group) {
-  check_cuda(A, "A");
-  check_cuda(B, "B");
-  check_cuda(out, "out");
+  const TensorArgs t("gemm", out, "out");
   TORCH_CHECK(A.scalar_type() == B.scalar_type(), "gemm: A and B dtypes differ");
-  const int dt = dtype_code(A);
+  TORCH_CHECK(a_ones_row < 0 || b_ones_row < 0, "gemm: at most one of a_ones_row / b_ones_row");
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && lda >= 0 && ldb >= 0 && ldc >= 0, "gemm: M, N, K >= 1 and leading dimensions >= 0");
+  // every kernel reads whole operand rows with no bounds checks beyond M / N / K: every element they may
+  // touch must lie inside the tensors.  A trailing ones row reads as 1.0 and has no memory behind it; with
+  // bias_out its output row / column goes there and not to out / aux / out2
+  const int64_t a_rows = a_ones_row == M - 1 ? M - 1 : M, b_rows = b_ones_row == N - 1 ? N - 1 : N;
+  const int64_t c_rows = has(bias_out) ? a_rows : M, c_cols = has(bias_out) ? b_rows : N;
+  const int64_t c_need = (c_rows - 1) * ldc + c_cols;
   dtfe::DenseGemmArgs a{};
   a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.A = A.data_ptr(); a.lda = lda;
-  a.B = B.data_ptr(); a.ldb = ldb;
+  const dtfe::AnyPtr pa = t.any(A, "A", dtfe::F32_OR_BF16, spans(amode == 0 ? (a_rows - 1) * lda + K : (K - 1) * lda + a_rows));
+  const int dt = pa.f32() ? 1 : 0;
+  a.A = pa.p; a.lda = lda;
+  a.B = t.any(B, "B", dtfe::F32_OR_BF16, spans(bmode == 0 ? (b_rows - 1) * ldb + K : (K - 1) * ldb + b_rows)).p;
+  a.ldb = ldb;
   a.b_ones_row = (int)b_ones_row;
   a.a_ones_row = (int)a_ones_row;
-  TORCH_CHECK(a_ones_row < 0 || b_ones_row < 0, "gemm: at most one of a_ones_row / b_ones_row");
   if (splits < 1) splits = 1;
   int bm = 0, bn = 0;
   const int kt = dtfe::gemm_dense_tile_dims((int)tile, bm, bn);
@@ -107,61 +110,55 @@ void gemm(const Tensor& A, int64_t amode, int64_t lda, const Tensor& B, int64_t 
   if (chunk < kt) chunk = kt;
   const int real_splits = (int)((K + chunk - 1) / chunk);
   a.k_chunk = chunk;
-  a.out = out.data_ptr(); a.ldc = ldc; a.out_f32 = out.scalar_type() == at::kFloat;
-  a.bias = ptr_or_null<float>(bias); a.bias_axis = (int)bias_axis;
+  a.unpool = has(pooled) ? 1 : 0;
+  if (a.unpool) {  // out is the bf16 [B][2PH][2PW][C] tensor that the pooled [M][N] gradient is routed into
+    TORCH_CHECK(has(argmax) && PH >= 1 && PW >= 1 && PC >= 1, "gemm: the unpool epilogue needs argmax and PH, PW, PC");
+    a.out = t.out<dtfe::bf16>(out, "out", at_least(4 * c_need));
+    a.up.pooled = t.in<dtfe::bf16>(pooled, "pooled", at_least(c_need));
+    a.up.argmax = t.in<uint8_t>(argmax, "argmax", at_least(c_need));
+    a.up.PH = (int)PH; a.up.PW = (int)PW; a.up.C = (int)PC;
+  } else {
+    const dtfe::AnyPtr po = t.any(out, "out", dtfe::F32_OR_BF16, spans(c_need));
+    a.out = po.p; a.out_f32 = po.f32();
+  }
+  a.ldc = ldc;
+  a.bias = t.in<float>(bias, "bias", at_least(bias_axis ? M : N)); a.bias_axis = (int)bias_axis;
   a.act = (int)act; a.alpha = (float)alpha; a.beta = (float)beta; a.atomic = atomic;
   if (real_splits > 1 && !atomic) {
     const int64_t ntiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    TORCH_CHECK(ws.has_value() && ws->defined() && tile_ctr.has_value() && tile_ctr->defined(),
-                "gemm: split-K with a fused epilogue needs ws/tile_ctr");
-    TORCH_CHECK(ws->scalar_type() == at::kFloat && ws->numel() >= real_splits * ntiles * bm * bn,
-                "gemm: split-K workspace too small");
-    TORCH_CHECK(tile_ctr->scalar_type() == at::kInt && tile_ctr->numel() >= ntiles, "gemm: tile counters too small");
-    a.ws = ws->data_ptr<float>();
-    a.tile_ctr = tile_ctr->data_ptr<int>();
+    TORCH_CHECK(has(ws) && has(tile_ctr), "gemm: split-K with a fused epilogue needs ws/tile_ctr");
+    a.ws = t.out<float>(ws, "ws (the split-K workspace)", at_least(real_splits * ntiles * bm * bn));
+    a.tile_ctr = t.out<int32_t>(tile_ctr, "tile_ctr (the split-K tile counters)", at_least(ntiles));
   }
   TORCH_CHECK(!atomic || a.out_f32, "gemm: atomic accumulation needs an fp32 output");
-  a.out2 = ptr_or_null<void>(out2); a.ldc2 = ldc2;
-  a.out2_f32 = (out2.has_value() && out2->defined()) ? out2->scalar_type() == at::kFloat : 0;
-  a.out2_trans = out2_trans;
-  a.aux = ptr_or_null<void>(aux); a.ld_aux = ld_aux;
-  a.aux_f32 = (aux.has_value() && aux->defined()) ? aux->scalar_type() == at::kFloat : 0;
-  a.aux_act = (int)aux_act;
-  a.unpool = (pooled.has_value() && pooled->defined()) ? 1 : 0;
-  if (a.unpool) {
-    TORCH_CHECK(out.scalar_type() == at::kBFloat16, "gemm: unpool epilogue writes bf16");
-    a.up.pooled = reinterpret_cast<const dtfe::bf16*>(pooled->data_ptr());
-    a.up.argmax = reinterpret_cast<const uint8_t*>(argmax->data_ptr());
-    a.up.PH = (int)PH; a.up.PW = (int)PW; a.up.C = (int)PC;
-  }
-  a.keep = (float)keep; a.seed = (uint64_t)seed; a.counter = ptr_or_null<int64_t>(counter);
-  a.bias_out = ptr_or_null<float>(bias_out);
+  const dtfe::AnyPtr p2 = t.any(out2, "out2", dtfe::F32_OR_BF16,
+                                spans(out2_trans ? (c_cols - 1) * ldc2 + c_rows : (c_rows - 1) * ldc2 + c_cols));
+  a.out2 = p2.p; a.ldc2 = ldc2; a.out2_f32 = p2.f32(); a.out2_trans = out2_trans;
+  const dtfe::AnyPtr px = t.any(aux, "aux", dtfe::F32_OR_BF16, spans((c_rows - 1) * ld_aux + c_cols));
+  a.aux = px.p; a.ld_aux = ld_aux; a.aux_f32 = px.f32(); a.aux_act = (int)aux_act;
+  a.keep = (float)keep; a.seed = (uint64_t)seed; a.counter = t.in<int64_t>(counter, "counter", at_least(1));
+  a.bias_out = t.out<float>(bias_out, "bias_out", at_least(a_ones_row >= 0 ? N : M));
   TORCH_CHECK(!a.bias_out || b_ones_row >= 0 || a_ones_row >= 0, "gemm: bias_out needs a ones row");
-  a.ones = ptr_or_null<dtfe::bf16>(ones);
+  a.ones = t.in<dtfe::bf16>(ones, "ones", at_least(512));  // the 1 KB page of ops.ones_page
   if (tile == dtfe::GEMM_TILE_SMALL) {
-    TORCH_CHECK(real_splits == 1 && dtfe::gemm_small_eligible(dt == 0 ? 0 : 1, a),
+    TORCH_CHECK(real_splits == 1 && dtfe::gemm_small_eligible(dt, a),
                 "gemm: the small-tile kernel takes fp32 operands, one split, no un-pool epilogue");
   } else if (tile >= 5) {
-    TORCH_CHECK(dtfe::gemm_glds_eligible(dt == 0 ? 0 : 1, (int)amode, (int)bmode, (int)tile, a),
+    TORCH_CHECK(dtfe::gemm_glds_eligible(dt, (int)amode, (int)bmode, (int)tile, a),
                 "gemm: shape / layout not eligible for the global_load_lds tile ", tile);
-    // the glds kernels load whole k-tiles of whole operand rows with no bounds checks: every element
-    // they may touch must lie inside the tensors
-    const int64_t b_rows = b_ones_row >= 0 ? b_ones_row : N;
-    const int64_t a_need = amode == 0 ? (M - 1) * lda + K : (K - 1) * lda + M;
-    const int64_t b_need = bmode == 0 ? (b_rows - 1) * ldb + K : (K - 1) * ldb + b_rows;
-    TORCH_CHECK(A.numel() >= a_need && B.numel() >= b_need, "gemm: operands smaller than M/N/K/ld imply");
   }
   auto add = [&](dtfe::GemmGroup& g) {
-    return dtfe::gemm_group_add(g, dt == 0 ? 0 : 1, (int)amode, (int)bmode, (int)tile, real_splits, a);
+    return dtfe::gemm_group_add(g, dt, (int)amode, (int)bmode, (int)tile, real_splits, a);
   };  // (a piece has one split: no ws / tile_ctr to hold)
   if (group.has_value() && (*group)->join(add, out, A, B, bias, aux, counter, pooled, argmax, out2, bias_out, ones))
     return;
-  dtfe::launch_gemm_dense(dt == 0 ? 0 : 1, (int)amode, (int)bmode, (int)tile, real_splits, a, cur_stream());
+  dtfe::launch_gemm_dense(dt, (int)amode, (int)bmode, (int)tile, real_splits, a, t.stream());
 }
 
 // ------------------------------------------------------------------- conv
 dtfe::ConvGeom geom(int64_t B, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t OH, int64_t OW, int64_t KH,
                     int64_t KW, int64_t stride, int64_t pad, int64_t pool) {
+  TORCH_CHECK(std::min({B, H, W, C, Cout, OH, OW, KH, KW, stride}) >= 1 && pad >= 0, "conv: geometry must be positive");
   dtfe::ConvGeom g;
   g.B = (int)B; g.H = (int)H; g.W = (int)W; g.C = (int)C; g.Cout = (int)Cout; g.OH = (int)OH; g.OW = (int)OW;
   g.KH = (int)KH; g.KW = (int)KW; g.stride = (int)stride; g.pad = (int)pad; g.pool_order = (int)pool;
@@ -172,35 +169,29 @@ void conv_fwd(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, co
               const optional<Tensor>& argmax, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Cout, int64_t OH,
               int64_t OW, int64_t KH, int64_t KW, int64_t stride, int64_t pad, bool pool, int64_t act,
               const optional<Tensor>& bn_stats) {
-  check_cuda(x, "x");
+  const TensorArgs t("conv_fwd", x, "x");
+  const int64_t nx = B * H * W * C, nw = Cout * KH * KW * C, ny = B * OH * OW * Cout / (pool ? 4 : 1);
   if (x.scalar_type() == at::kFloat) {  // exact-fp32 path (--dtype fp32): conv_f32.hip
-    TORCH_CHECK(w.scalar_type() == at::kFloat && y.scalar_type() == at::kFloat && !(bn_stats.has_value() && bn_stats->defined()),
-                "conv_fwd (fp32): fp32 x / w / y, no BatchNorm statistics");
+    TORCH_CHECK(!has(bn_stats), "conv_fwd (fp32): fp32 x / w / y, no BatchNorm statistics");
     TORCH_CHECK(!pool || ((OH | OW) & 1) == 0, "conv_fwd (fp32): pool needs even output dims");
     dtfe::ConvF32Args f{};
     f.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, pool);
-    f.src = x.data_ptr<float>(); f.w = w.data_ptr<float>(); f.bias = ptr_or_null<float>(bias);
-    f.out = y.data_ptr<float>(); f.argmax = ptr_or_null<uint8_t>(argmax); f.act = (int)act;
-    TORCH_CHECK(y.numel() == B * OH * OW * Cout / (pool ? 4 : 1) && x.numel() == B * H * W * C &&
-                w.numel() == Cout * KH * KW * C, "conv_fwd (fp32): shapes");
-    dtfe::launch_conv_fwd_f32(f, cur_stream());
+    f.src = t.in<float>(x, "x", exactly(nx)); f.w = t.in<float>(w, "w", exactly(nw));
+    f.bias = t.in<float>(bias, "bias", at_least(Cout));
+    f.out = t.out<float>(y, "y", exactly(ny)); f.argmax = t.out<uint8_t>(argmax, "argmax", at_least(ny)); f.act = (int)act;
+    dtfe::launch_conv_fwd_f32(f, t.stream());
     return;
   }
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "conv_fwd: bf16 or fp32");
   dtfe::ConvFwdArgs a{};
-  if (bn_stats.has_value() && bn_stats->defined()) {
-    TORCH_CHECK(bn_stats->scalar_type() == at::kFloat && bn_stats->is_contiguous() && bn_stats->numel() >= 2 * Cout,
-                "conv_fwd: bn_stats must be f32 [2][Cout]");
-    a.bn_stats = bn_stats->data_ptr<float>();
-  }
+  a.bn_stats = t.out<float>(bn_stats, "bn_stats", at_least(2 * Cout));
   a.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, pool);
-  a.x = reinterpret_cast<const dtfe::bf16*>(x.data_ptr());
-  a.w = reinterpret_cast<const dtfe::bf16*>(w.data_ptr());
-  a.bias = ptr_or_null<float>(bias);
-  a.y = reinterpret_cast<dtfe::bf16*>(y.data_ptr());
-  a.argmax = ptr_or_null<uint8_t>(argmax);
+  a.x = t.in<dtfe::bf16>(x, "x", at_least(nx));
+  a.w = t.in<dtfe::bf16>(w, "w", at_least(nw));
+  a.bias = t.in<float>(bias, "bias", at_least(Cout));
+  a.y = t.out<dtfe::bf16>(y, "y", at_least(ny));
+  a.argmax = t.out<uint8_t>(argmax, "argmax", at_least(ny));
   a.act = (int)act;
-  dtfe::launch_conv_fwd(a, cur_stream());
+  dtfe::launch_conv_fwd(a, t.stream());
 }
 
 void conv_dgrad(const Tensor& dy, const Tensor& wt, const Tensor& dx, int64_t B, int64_t H, int64_t W, int64_t C,
@@ -210,87 +201,84 @@ void conv_dgrad(const Tensor& dy, const Tensor& wt, const Tensor& dx, int64_t B,
                 const optional<Tensor>& bnb_mean, const optional<Tensor>& bnb_invstd, const optional<Tensor>& bnb_gamma,
                 const optional<Tensor>& bnb_beta, const optional<Tensor>& bnb_stats, int64_t bnb_act,
                 const optional<Tensor>& acc_src, const optional<Tensor>& acc_mask) {
-  check_cuda(dy, "dy");
+  const TensorArgs t("conv_dgrad", dy, "dy");
+  const int64_t ndx = B * H * W * C, ndy = B * OH * OW * Cout, nw = C * KH * KW * Cout;
   if (dy.scalar_type() == at::kFloat) {  // exact-fp32 path (--dtype fp32): conv_f32.hip
-    TORCH_CHECK(wt.scalar_type() == at::kFloat && dx.scalar_type() == at::kFloat && stride == 1 && !accumulate &&
-                    !(pooled.has_value() && pooled->defined()) && !(bnb_stats.has_value() && bnb_stats->defined()),
+    TORCH_CHECK(stride == 1 && !accumulate && !has(pooled) && !has(bnb_stats),
                 "conv_dgrad (fp32): fp32 tensors, stride 1, optional ReLU mask only");
-    TORCH_CHECK(dx.numel() == B * H * W * C && dy.numel() == B * OH * OW * Cout && wt.numel() == C * KH * KW * Cout,
-                "conv_dgrad (fp32): shapes");
     dtfe::ConvF32Args f{};
     f.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, 0);
-    f.src = dy.data_ptr<float>(); f.w = wt.data_ptr<float>(); f.out = dx.data_ptr<float>();
-    if (relu_mask.has_value() && relu_mask->defined()) {
-      TORCH_CHECK(relu_mask->scalar_type() == at::kFloat && relu_mask->numel() == dx.numel(), "conv_dgrad (fp32): mask");
-      f.relu_mask = relu_mask->data_ptr<float>();
-    }
-    dtfe::launch_conv_dgrad_f32(f, cur_stream());
+    f.src = t.in<float>(dy, "dy", exactly(ndy)); f.w = t.in<float>(wt, "wt", exactly(nw));
+    f.out = t.out<float>(dx, "dx", exactly(ndx));
+    f.relu_mask = t.in<float>(relu_mask, "relu_mask", exactly(ndx));
+    dtfe::launch_conv_dgrad_f32(f, t.stream());
     return;
   }
   dtfe::ConvDgradArgs a{};
   a.accumulate = accumulate ? 1 : 0;
-  if (bnb_stats.has_value() && bnb_stats->defined()) {
-    TORCH_CHECK(bnb_x.has_value() && bnb_x->defined() && bnb_mean.has_value() && bnb_invstd.has_value() &&
-                    bnb_gamma.has_value(), "conv_dgrad: BN-backward statistics need x, mean, invstd, gamma");
-    TORCH_CHECK(bnb_x->numel() == dx.numel() && bnb_x->scalar_type() == at::kBFloat16, "conv_dgrad: bnb_x shape/dtype");
-    TORCH_CHECK(bnb_stats->numel() >= 2 * C && bnb_stats->scalar_type() == at::kFloat, "conv_dgrad: bnb_stats [2][C] fp32");
-    TORCH_CHECK(bnb_mean->numel() >= C && bnb_invstd->numel() >= C && bnb_gamma->numel() >= C, "conv_dgrad: BN params");
-    const bool bits = bnb_y.has_value() && bnb_y->defined() && bnb_y->scalar_type() == at::kByte;
-    if (bnb_y.has_value() && bnb_y->defined())
-      TORCH_CHECK(bits ? bnb_y->numel() == dx.numel() / 8 : (bnb_y->numel() == dx.numel() && bnb_y->scalar_type() == at::kBFloat16),
-                  "conv_dgrad: bnb_y shape/dtype (bf16 output, or its uint8 [R][C/8] ReLU bit mask)");
-    if (bnb_beta.has_value() && bnb_beta->defined()) TORCH_CHECK(bnb_beta->numel() >= C, "conv_dgrad: bnb_beta");
-    a.bnb_x = reinterpret_cast<const dtfe::bf16*>(bnb_x->data_ptr());
-    if (bits) a.bnb_ymask = bnb_y->data_ptr<uint8_t>();
-    else a.bnb_y = ptr_or_null<dtfe::bf16>(bnb_y);
-    a.bnb_mean = bnb_mean->data_ptr<float>();
-    a.bnb_invstd = bnb_invstd->data_ptr<float>();
-    a.bnb_gamma = bnb_gamma->data_ptr<float>();
-    a.bnb_beta = ptr_or_null<float>(bnb_beta);
-    a.bnb_stats = bnb_stats->data_ptr<float>();
+  a.unpool = has(pooled) ? 1 : 0;
+  // with the un-pool epilogue [B][H][W][C] is the pooled tensor and dx its [B][2H][2W][C] source
+  const int64_t nout = a.unpool ? 4 * ndx : ndx;
+  if (has(bnb_stats)) {
+    TORCH_CHECK(has(bnb_x) && has(bnb_mean) && has(bnb_invstd) && has(bnb_gamma),
+                "conv_dgrad: BN-backward statistics need x, mean, invstd, gamma");
+    a.bnb_x = t.in<dtfe::bf16>(bnb_x, "bnb_x", exactly(dx.numel()));
+    // the forward output (bf16), or its uint8 [R][C/8] ReLU bit mask
+    if (has(bnb_y) && bnb_y->scalar_type() == at::kByte) a.bnb_ymask = t.in<uint8_t>(bnb_y, "bnb_y", exactly(dx.numel() / 8));
+    else a.bnb_y = t.in<dtfe::bf16>(bnb_y, "bnb_y", exactly(dx.numel()));
+    a.bnb_mean = t.in<float>(bnb_mean, "bnb_mean", at_least(C));
+    a.bnb_invstd = t.in<float>(bnb_invstd, "bnb_invstd", at_least(C));
+    a.bnb_gamma = t.in<float>(bnb_gamma, "bnb_gamma", at_least(C));
+    a.bnb_beta = t.in<float>(bnb_beta, "bnb_beta", at_least(C));
+    a.bnb_stats = t.out<float>(bnb_stats, "bnb_stats", at_least(2 * C));
     a.bnb_act = (int)bnb_act;
   }
-  if (acc_src.has_value() && acc_src->defined()) {
-    TORCH_CHECK(accumulate && acc_src->numel() == dx.numel() && acc_src->scalar_type() == at::kBFloat16 &&
-                    acc_mask.has_value() && acc_mask->defined() && acc_mask->scalar_type() == at::kByte &&
-                    acc_mask->numel() == dx.numel() / 8,
-                "conv_dgrad: acc_src (bf16, dx's shape) needs accumulate and its uint8 [R][C/8] bit mask");
-    a.acc_src = reinterpret_cast<const dtfe::bf16*>(acc_src->data_ptr());
-    a.acc_mask = acc_mask->data_ptr<uint8_t>();
+  if (has(acc_src)) {
+    TORCH_CHECK(accumulate && has(acc_mask), "conv_dgrad: acc_src (bf16, dx's shape) needs accumulate and its uint8 [R][C/8] bit mask");
+    a.acc_src = t.in<dtfe::bf16>(acc_src, "acc_src", exactly(dx.numel()));
+    a.acc_mask = t.in<uint8_t>(acc_mask, "acc_mask", exactly(dx.numel() / 8));
   }
   a.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, 0);
-  a.dy = reinterpret_cast<const dtfe::bf16*>(dy.data_ptr());
-  a.wt = reinterpret_cast<const dtfe::bf16*>(wt.data_ptr());
-  a.dx = reinterpret_cast<dtfe::bf16*>(dx.data_ptr());
-  a.relu_mask = ptr_or_null<dtfe::bf16>(relu_mask);
-  a.unpool = (pooled.has_value() && pooled->defined()) ? 1 : 0;
+  a.dy = t.in<dtfe::bf16>(dy, "dy", at_least(ndy));
+  a.wt = t.in<dtfe::bf16>(wt, "wt", at_least(nw));
+  a.dx = t.out<dtfe::bf16>(dx, "dx", at_least(nout));
+  a.relu_mask = t.in<dtfe::bf16>(relu_mask, "relu_mask", at_least(ndx));
   if (a.unpool) {
-    a.up.pooled = reinterpret_cast<const dtfe::bf16*>(pooled->data_ptr());
-    a.up.argmax = reinterpret_cast<const uint8_t*>(argmax->data_ptr());
+    TORCH_CHECK(has(argmax), "conv_dgrad: pooled needs argmax");
+    a.up.pooled = t.in<dtfe::bf16>(pooled, "pooled", at_least(ndx));
+    a.up.argmax = t.in<uint8_t>(argmax, "argmax", at_least(ndx));
     a.up.PH = (int)H; a.up.PW = (int)W; a.up.C = (int)C;
   }
-  dtfe::launch_conv_dgrad(a, cur_stream());
+  dtfe::launch_conv_dgrad(a, t.stream());
 }
 
 // [stats, gamma, beta, mean, invstd, moving_mean, moving_var] of a BatchNorm + ReLU formed on a
 // whole-image conv's source (the last four may be undefined: nothing saved / updated)
-dtfe::BnSrc bn_src_of(const optional<at::TensorList>& t, long R, int64_t C, double eps, double momentum, bool save) {
+dtfe::BnSrc bn_src_of(const TensorArgs& t, const optional<at::TensorList>& l, long R, int64_t C, double eps,
+                      double momentum, bool save) {
   dtfe::BnSrc b{};
-  if (!t.has_value() || t->empty()) return b;
-  TORCH_CHECK(t->size() == 7, "bn_src: [stats, gamma, beta, mean, invstd, moving_mean, moving_var]");
-  const auto& v = *t;
-  for (int i = 0; i < 3; ++i) {
-    check_cuda(v[i], "bn_src");
-    TORCH_CHECK(v[i].scalar_type() == at::kFloat && v[i].numel() >= (i == 0 ? 2 : 1) * C, "bn_src: fp32 [C] / [2][C]");
-  }
-  b.stats = v[0].data_ptr<float>();
-  b.gamma = v[1].data_ptr<float>();
-  b.beta = v[2].data_ptr<float>();
-  auto opt = [&](int i) { return save && v[i].defined() ? v[i].data_ptr<float>() : nullptr; };
-  b.mean = opt(3); b.invstd = opt(4); b.moving_mean = opt(5); b.moving_var = opt(6);
+  if (!l.has_value() || l->empty()) return b;
+  TORCH_CHECK(l->size() == 7, "bn_src: [stats, gamma, beta, mean, invstd, moving_mean, moving_var]");
+  const auto& v = *l;
+  b.stats = t.out<float>(v[0], "bn_src[0] (stats)", at_least(2 * C));
+  b.gamma = t.in<float>(v[1], "bn_src[1] (gamma)", at_least(C));
+  b.beta = t.in<float>(v[2], "bn_src[2] (beta)", at_least(C));
+  static const char* const names[7] = {"", "", "", "bn_src[3] (mean)", "bn_src[4] (invstd)", "bn_src[5] (moving_mean)",
+                                       "bn_src[6] (moving_var)"};
+  auto saved = [&](int i) { return save && v[i].defined() ? t.out<float>(v[i], names[i], at_least(C)) : nullptr; };
+  b.mean = saved(3); b.invstd = saved(4); b.moving_mean = saved(5); b.moving_var = saved(6);
   TORCH_CHECK((b.moving_mean == nullptr) == (b.moving_var == nullptr), "bn_src: both moving averages or neither");
   b.R = R; b.eps = (float)eps; b.momentum = (float)momentum;
   return b;
+}
+
+// the B .. pad geometry fields that ImgConvArgs and ImgWgradArgs share
+template <typename A>
+void img_geom(A& a, int64_t B, int64_t SH, int64_t SW, int64_t CS, int64_t OH, int64_t OW, int64_t N, int64_t KH,
+              int64_t KW, int64_t stride, int64_t pad) {
+  TORCH_CHECK(std::min({B, SH, SW, CS, OH, OW, N, KH, KW, stride}) >= 1 && pad >= 0, "imgconv: geometry must be positive");
+  a.B = (int)B; a.SH = (int)SH; a.SW = (int)SW; a.CS = (int)CS; a.OH = (int)OH; a.OW = (int)OW; a.N = (int)N;
+  a.KH = (int)KH; a.KW = (int)KW; a.stride = (int)stride; a.pad = (int)pad;
 }
 
 bool imgconv(const optional<Tensor>& src, const optional<Tensor>& src_pooled, const optional<Tensor>& src_argmax,
@@ -299,82 +287,75 @@ bool imgconv(const optional<Tensor>& src, const optional<Tensor>& src_pooled, co
              int64_t N, int64_t KH, int64_t KW, int64_t stride, int64_t pad, bool flip_taps, int64_t act, bool pool,
              int64_t dil, const optional<Tensor>& sc_src, int64_t sc_stride, const optional<Tensor>& tstamp,
              const optional<at::TensorList>& bn_src, double bn_eps, double bn_momentum, bool bn_save) {
-  check_cuda(w, "w");
-  TORCH_CHECK((src.has_value() && src->defined()) != (src_pooled.has_value() && src_pooled->defined()),
-              "imgconv: exactly one of src / src_pooled");
+  const TensorArgs t("imgconv", w, "w");
+  TORCH_CHECK(has(src) != has(src_pooled), "imgconv: exactly one of src / src_pooled");
+  TORCH_CHECK(has(src) || has(src_argmax), "imgconv: src_pooled needs src_argmax");
   dtfe::ImgConvArgs a{};
-  a.B = (int)B; a.SH = (int)SH; a.SW = (int)SW; a.CS = (int)CS; a.OH = (int)OH; a.OW = (int)OW; a.N = (int)N;
-  a.KH = (int)KH; a.KW = (int)KW; a.stride = (int)stride; a.pad = (int)pad; a.flip_taps = flip_taps;
+  img_geom(a, B, SH, SW, CS, OH, OW, N, KH, KW, stride, pad);
+  a.flip_taps = flip_taps;
   a.dil = (int)dil;
-  a.src = ptr_or_null<dtfe::bf16>(src);
-  a.src_pooled = ptr_or_null<dtfe::bf16>(src_pooled);
-  a.src_argmax = ptr_or_null<uint8_t>(src_argmax);
-  TORCH_CHECK(a.src || a.src_argmax, "imgconv: src_pooled needs src_argmax");
-  a.w = reinterpret_cast<const dtfe::bf16*>(w.data_ptr());
-  a.bias = ptr_or_null<float>(bias);
+  const int64_t ny = B * OH * OW * N / (pool ? 4 : 1), npooled = B * (SH / 2) * (SW / 2) * CS;
+  a.src = t.in<dtfe::bf16>(src, "src", at_least(B * SH * SW * CS));
+  a.src_pooled = t.in<dtfe::bf16>(src_pooled, "src_pooled", at_least(npooled));
+  a.src_argmax = t.in<uint8_t>(src_argmax, "src_argmax", at_least(npooled));
+  a.w = t.in<dtfe::bf16>(w, "w", exactly(N * KH * KW * CS));
+  a.bias = t.in<float>(bias, "bias", at_least(N));
   a.act = (int)act; a.pool = pool;
-  a.y = reinterpret_cast<dtfe::bf16*>(y.data_ptr());
-  a.argmax = ptr_or_null<uint8_t>(argmax);
-  a.relu_mask = ptr_or_null<dtfe::bf16>(relu_mask);
-  TORCH_CHECK(w.numel() == N * KH * KW * CS, "imgconv: weight size");
-  TORCH_CHECK(y.numel() == B * OH * OW * N / (pool ? 4 : 1), "imgconv: output size");
-  a.tstamp = tstamp.has_value() && tstamp->defined() ? reinterpret_cast<uint64_t*>(tstamp->data_ptr()) : nullptr;
-  a.bns = bn_src_of(bn_src, (long)B * SH * SW, CS, bn_eps, bn_momentum, bn_save);
+  a.y = t.out<dtfe::bf16>(y, "y", exactly(ny));
+  a.argmax = t.out<uint8_t>(argmax, "argmax", at_least(ny));
+  a.relu_mask = t.in<dtfe::bf16>(relu_mask, "relu_mask", at_least(ny));
+  a.tstamp = t.out<uint64_t>(tstamp, "tstamp", at_least(8 * std::min<int64_t>(B, 256)));  // [grid][8]
+  a.bns = bn_src_of(t, bn_src, (long)B * SH * SW, CS, bn_eps, bn_momentum, bn_save);
   TORCH_CHECK(!a.bns.stats || a.src, "imgconv: BN-on-load needs a plain source");
-  a.sc_src = ptr_or_null<dtfe::bf16>(sc_src);
-  if (a.sc_src) {
+  if (has(sc_src)) {
     TORCH_CHECK(sc_stride >= 1 && OH % sc_stride == 0 && OW % sc_stride == 0 && sc_src->dim() == 4 &&
                     sc_src->size(0) == B && sc_src->size(1) == OH / sc_stride && sc_src->size(2) == OW / sc_stride &&
                     sc_src->size(3) >= N,
                 "imgconv: shortcut gradient [B][OH/s][OW/s][>= N]");
+    a.sc_src = t.in<dtfe::bf16>(sc_src, "sc_src", exactly(sc_src->numel()));
     a.sc_stride = (int)sc_stride;
     a.sc_C = (int)sc_src->size(3);
   }
-  return dtfe::launch_imgconv(a, cur_stream());
+  return dtfe::launch_imgconv(a, t.stream());
 }
 
 // MNIST conv1 forward with the step's batch sampling fused in (imgconv1_copies.hip): samples B rows
 // of the uint8 dataset, writes the bf16 images to x (the weight gradient's input) and the labels,
 // clears the accumulators in `zero`, and runs conv1 + bias + ReLU + 2x2 max-pool(+argmax).
-dtfe::ImgConvArgs conv1_gather_args(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
-                                    const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
-                                    const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax,
+dtfe::ImgConvArgs conv1_gather_args(const TensorArgs& t, const Tensor& images, const Tensor& labels_src, int64_t seed,
+                                    const Tensor& counter, const Tensor& done, const Tensor& labels_dst, const Tensor& x,
+                                    const Tensor& w, const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax,
                                     at::TensorList zero) {
-  check_cuda(images, "images");
-  TORCH_CHECK(images.scalar_type() == at::kByte && images.dim() == 2 && images.size(1) == 784,
-              "conv1_gather_fwd: uint8 [rows][784] dataset");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.numel() % 784 == 0, "conv1_gather_fwd: bf16 x [B][28][28]");
+  TORCH_CHECK(images.dim() == 2 && images.size(1) == 784 && images.size(0) >= 1, "conv1_gather_fwd: uint8 [rows][784] dataset");
+  TORCH_CHECK(x.numel() % 784 == 0 && x.numel() >= 784, "conv1_gather_fwd: bf16 x [B][28][28]");
   dtfe::ImgConvArgs a{};
-  a.B = (int)(x.numel() / 784); a.SH = a.SW = 28; a.CS = 1; a.OH = a.OW = 28; a.N = 32;
-  a.KH = a.KW = 5; a.stride = 1; a.pad = 2; a.dil = 1;
-  a.src = reinterpret_cast<const dtfe::bf16*>(x.data_ptr());
-  a.w = reinterpret_cast<const dtfe::bf16*>(w.data_ptr());
-  a.bias = ptr_or_null<float>(bias);
+  const int64_t B = x.numel() / 784;
+  img_geom(a, B, 28, 28, 1, 28, 28, 32, 5, 5, 1, 2);
+  a.dil = 1;
+  a.src = t.out<dtfe::bf16>(x, "x", exactly(B * 784));
+  a.w = t.in<dtfe::bf16>(w, "w", exactly(32 * 25));
+  a.bias = t.in<float>(bias, "bias", at_least(32));
   a.act = dtfe::ACT_RELU; a.pool = 1;
-  a.y = reinterpret_cast<dtfe::bf16*>(y.data_ptr());
-  a.argmax = reinterpret_cast<uint8_t*>(argmax.data_ptr());
-  TORCH_CHECK(w.numel() == 32 * 25 && y.numel() == (int64_t)a.B * 14 * 14 * 32 && argmax.numel() == y.numel(),
-              "conv1_gather_fwd: MNIST conv1 shapes");
-  a.g_src = images.data_ptr<uint8_t>(); a.g_rows = images.size(0); a.g_seed = (uint64_t)seed;
+  a.y = t.out<dtfe::bf16>(y, "y", exactly(B * 14 * 14 * 32));
+  a.argmax = t.out<uint8_t>(argmax, "argmax", exactly(B * 14 * 14 * 32));
+  a.g_src = t.in<uint8_t>(images, "images", exactly(images.size(0) * 784)); a.g_rows = images.size(0);
+  a.g_seed = (uint64_t)seed;
   // an empty `done` leaves the counter alone (the caller advances it later in the step)
-  a.g_counter = counter.data_ptr<int64_t>();
-  a.g_done = done.numel() ? reinterpret_cast<uint32_t*>(done.data_ptr()) : nullptr;
-  a.g_labels_src = labels_src.data_ptr<int32_t>(); a.g_labels_dst = labels_dst.data_ptr<int32_t>();
-  TORCH_CHECK(zero.size() <= 4, "conv1_gather_fwd: at most 4 zero ranges");
-  for (const Tensor& z : zero) {
-    TORCH_CHECK(z.is_contiguous() && (z.numel() * z.element_size()) % 4 == 0, "conv1_gather_fwd: zero ranges");
-    a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
-    a.zlen[a.nz++] = (long)(z.numel() * z.element_size() / 4);
-  }
+  a.g_counter = t.out<int64_t>(counter, "counter", at_least(1));
+  a.g_done = done.numel() ? t.out<uint32_t>(done, "done", at_least(1)) : nullptr;
+  a.g_labels_src = t.in<int32_t>(labels_src, "labels_src", at_least(a.g_rows));
+  a.g_labels_dst = t.out<int32_t>(labels_dst, "labels_dst", at_least(B));
+  t.zero_ranges(zero, a.zptr, a.zlen, a.nz);
   return a;
 }
 
 void conv1_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t seed, const Tensor& counter,
                       const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
                       const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax, at::TensorList zero) {
-  const dtfe::ImgConvArgs a = conv1_gather_args(images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
+  const TensorArgs t("conv1_gather_fwd", images, "images");
+  const dtfe::ImgConvArgs a = conv1_gather_args(t, images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
                                                 argmax, zero);
-  TORCH_CHECK(dtfe::launch_conv1_copies_fwd(a, cur_stream()), "conv1_gather_fwd: needs B >= 256");
+  TORCH_CHECK(dtfe::launch_conv1_copies_fwd(a, t.stream()), "conv1_gather_fwd: needs B >= 256");
 }
 
 // conv1_gather_fwd and MNIST conv2's forward (w2 [64][25][32], +bias, ReLU, 2x2 max-pool(+argmax) -> p2 / a2)
@@ -384,24 +365,14 @@ void conv12_gather_fwd(const Tensor& images, const Tensor& labels_src, int64_t s
                        const Tensor& done, const Tensor& labels_dst, const Tensor& x, const Tensor& w,
                        const optional<Tensor>& bias, const Tensor& y, const Tensor& argmax, at::TensorList zero,
                        const Tensor& w2, const optional<Tensor>& bias2, const Tensor& p2, const Tensor& a2) {
-  const dtfe::ImgConvArgs a = conv1_gather_args(images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
+  const TensorArgs t("conv12_gather_fwd", images, "images");
+  const dtfe::ImgConvArgs a = conv1_gather_args(t, images, labels_src, seed, counter, done, labels_dst, x, w, bias, y,
                                                 argmax, zero);
-  check_cuda(w2, "w2");
-  check_cuda(p2, "p2");
-  check_cuda(a2, "a2");
-  TORCH_CHECK(w2.scalar_type() == at::kBFloat16 && w2.is_contiguous() && w2.numel() == 64 * 25 * 32,
-              "conv12_gather_fwd: bf16 conv2 weight [64][5*5][32]");
-  TORCH_CHECK(p2.scalar_type() == at::kBFloat16 && p2.is_contiguous() && p2.numel() == (int64_t)a.B * 7 * 7 * 64,
-              "conv12_gather_fwd: bf16 p2 [B][7][7][64]");
-  TORCH_CHECK(a2.scalar_type() == at::kByte && a2.is_contiguous() && a2.numel() == p2.numel(),
-              "conv12_gather_fwd: uint8 a2 [B][7][7][64]");
-  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && argmax.scalar_type() == at::kByte && w.scalar_type() == at::kBFloat16,
-              "conv12_gather_fwd: bf16 p1 / conv1 weight, uint8 a1");
-  if (bias2.has_value() && bias2->defined())
-    TORCH_CHECK(bias2->scalar_type() == at::kFloat && bias2->numel() >= 64, "conv12_gather_fwd: fp32 conv2 bias [64]");
-  TORCH_CHECK(dtfe::launch_conv12_fused_fwd(a, reinterpret_cast<const dtfe::bf16*>(w2.data_ptr()),
-                                            ptr_or_null<float>(bias2), reinterpret_cast<dtfe::bf16*>(p2.data_ptr()),
-                                            a2.data_ptr<uint8_t>(), cur_stream()),
+  const int64_t n2 = (int64_t)a.B * 7 * 7 * 64;
+  TORCH_CHECK(dtfe::launch_conv12_fused_fwd(a, t.in<dtfe::bf16>(w2, "w2", exactly(64 * 25 * 32)),
+                                            t.in<float>(bias2, "bias2", at_least(64)),
+                                            t.out<dtfe::bf16>(p2, "p2", exactly(n2)), t.out<uint8_t>(a2, "a2", exactly(n2)),
+                                            t.stream()),
               "conv12_gather_fwd: needs B >= 256");
 }
 
@@ -413,29 +384,25 @@ std::vector<int64_t> imgwgrad(const Tensor& src, const optional<Tensor>& dy, con
                               int64_t KH, int64_t KW, int64_t stride, int64_t pad, double scale,
                               const optional<Tensor>& ws, int64_t max_blocks, const optional<at::TensorList>& bn_src,
                               double bn_eps, bool defer) {
-  check_cuda(src, "src");
+  const TensorArgs t("imgwgrad", src, "src");
   dtfe::ImgWgradArgs a{};
+  img_geom(a, B, SH, SW, CS, OH, OW, N, KH, KW, stride, pad);
   a.defer_reduce = defer ? 1 : 0;
-  a.bns = bn_src_of(bn_src, (long)B * SH * SW, CS, bn_eps, 0.0, false);
+  a.bns = bn_src_of(t, bn_src, (long)B * SH * SW, CS, bn_eps, 0.0, false);
   a.max_blocks = (int)max_blocks;
-  if (ws.has_value() && ws->defined()) {
-    TORCH_CHECK(ws->scalar_type() == at::kFloat && ws->numel() >= dtfe::imgwgrad_ws_floats((int)N, (int)(KH * KW * CS)),
-                "imgwgrad: workspace too small (ops.wgrad_ws_floats)");
-    a.ws = ws->data_ptr<float>();
-  }
-  a.B = (int)B; a.SH = (int)SH; a.SW = (int)SW; a.CS = (int)CS; a.OH = (int)OH; a.OW = (int)OW; a.N = (int)N;
-  a.KH = (int)KH; a.KW = (int)KW; a.stride = (int)stride; a.pad = (int)pad;
-  a.src = reinterpret_cast<const dtfe::bf16*>(src.data_ptr());
-  a.dy = ptr_or_null<dtfe::bf16>(dy);
-  a.dy_pooled = ptr_or_null<dtfe::bf16>(dy_pooled);
-  a.dy_argmax = ptr_or_null<uint8_t>(dy_argmax);
+  a.ws = t.out<float>(ws, "ws (ops.wgrad_ws_floats)", at_least(dtfe::imgwgrad_ws_floats((int)N, (int)(KH * KW * CS))));
+  const int64_t npooled = B * (OH / 2) * (OW / 2) * N;
+  a.src = t.in<dtfe::bf16>(src, "src", at_least(B * SH * SW * CS));
+  a.dy = t.in<dtfe::bf16>(dy, "dy", at_least(B * OH * OW * N));
+  a.dy_pooled = t.in<dtfe::bf16>(dy_pooled, "dy_pooled", at_least(npooled));
+  a.dy_argmax = t.in<uint8_t>(dy_argmax, "dy_argmax", at_least(npooled));
   TORCH_CHECK((a.dy != nullptr) != (a.dy_pooled != nullptr), "imgwgrad: exactly one of dy / dy_pooled");
-  TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.numel() == N * KH * KW * CS, "imgwgrad: dw");
-  a.dw = dw.data_ptr<float>();
-  a.db = ptr_or_null<float>(db);
+  TORCH_CHECK(a.dy || a.dy_argmax, "imgwgrad: dy_pooled needs dy_argmax");
+  a.dw = t.out<float>(dw, "dw", exactly(N * KH * KW * CS));
+  a.db = t.out<float>(db, "db", at_least(N));
   a.scale = (float)scale;
   dtfe::WpReduceItem r;
-  dtfe::launch_imgwgrad(a, cur_stream(), r);
+  dtfe::launch_imgwgrad(a, t.stream(), r);
   if (r.nblk == 0) return {};
   return {r.nblk, r.plen, r.MT, r.CTW, r.KC, r.N};
 }
@@ -448,83 +415,71 @@ void wgrad_reduce_group(at::TensorList ws, at::TensorList dw, const c10::List<op
   TORCH_CHECK(n <= (size_t)dtfe::WP_GROUP_MAX, "wgrad_reduce_group: at most ", dtfe::WP_GROUP_MAX, " reduces");
   TORCH_CHECK(dw.size() == n && db.size() == n && scale.size() == n && desc.size() == 6 * n,
               "wgrad_reduce_group: one entry per reduce in every list");
+  if (n == 0) return;
+  const TensorArgs t("wgrad_reduce_group", ws[0], "ws");
   dtfe::WpReduceItem it[dtfe::WP_GROUP_MAX];
   for (size_t i = 0; i < n; ++i) {
     const int64_t* d = desc.data() + 6 * i;
     const optional<Tensor> b = db.get(i);
-    check_cuda(ws[i], "ws");
-    check_cuda(dw[i], "dw");
-    TORCH_CHECK(ws[i].scalar_type() == at::kFloat && dw[i].scalar_type() == at::kFloat && d[0] > 0 && d[1] > 0 &&
-                    ws[i].numel() >= d[0] * d[1] && dw[i].numel() == d[5] * d[4],
-                "wgrad_reduce_group: fp32 ws [>= nblk * plen] and dw [N * KC]");
-    TORCH_CHECK(!b || (b->is_cuda() && b->scalar_type() == at::kFloat && b->numel() >= d[5]),
-                "wgrad_reduce_group: fp32 db [N]");
-    it[i] = dtfe::WpReduceItem{ws[i].data_ptr<float>(), dw[i].data_ptr<float>(), ptr_or_null<float>(b), (float)scale[i],
+    TORCH_CHECK(d[0] > 0 && d[1] > 0 && d[4] > 0 && d[5] > 0, "wgrad_reduce_group: a descriptor of imgwgrad(defer=True)");
+    it[i] = dtfe::WpReduceItem{t.in<float>(ws[i], "ws", at_least(d[0] * d[1])), t.out<float>(dw[i], "dw", exactly(d[5] * d[4])),
+                               t.out<float>(b, "db", at_least(d[5])), (float)scale[i],
                                (int)d[0], (int)d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5]};
   }
-  dtfe::launch_wgrad_reduce_group(it, (int)n, cur_stream());
+  dtfe::launch_wgrad_reduce_group(it, (int)n, t.stream());
 }
 
 void conv_wgrad(const Tensor& dz, const Tensor& x, const Tensor& dw, const optional<Tensor>& db, int64_t B, int64_t H,
                 int64_t W, int64_t C, int64_t Cout, int64_t OH, int64_t OW, int64_t KH, int64_t KW, int64_t stride,
                 int64_t pad, double scale) {
-  check_cuda(dz, "dz");
-  TORCH_CHECK(dw.scalar_type() == at::kFloat, "conv_wgrad: fp32 grad buffer");
+  const TensorArgs t("conv_wgrad", dz, "dz");
+  const int64_t ndz = B * OH * OW * Cout, nx = B * H * W * C, nw = Cout * KH * KW * C;
   if (dz.scalar_type() == at::kFloat) {  // exact-fp32 path (--dtype fp32): conv_f32.hip
-    TORCH_CHECK(x.scalar_type() == at::kFloat && dz.numel() == B * OH * OW * Cout && x.numel() == B * H * W * C &&
-                    dw.numel() == Cout * KH * KW * C, "conv_wgrad (fp32): fp32 dz / x, shapes");
     dtfe::ConvF32Args f{};
     f.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, 0);
-    f.src = dz.data_ptr<float>(); f.x = x.data_ptr<float>(); f.dw = dw.data_ptr<float>();
-    f.db = ptr_or_null<float>(db); f.scale = (float)scale;
-    dtfe::launch_conv_wgrad_f32(f, cur_stream());
+    f.src = t.in<float>(dz, "dz", exactly(ndz)); f.x = t.in<float>(x, "x", exactly(nx));
+    f.dw = t.out<float>(dw, "dw", exactly(nw));
+    f.db = t.out<float>(db, "db", at_least(Cout)); f.scale = (float)scale;
+    dtfe::launch_conv_wgrad_f32(f, t.stream());
     return;
   }
   dtfe::ConvWgradArgs a{};
   a.g = geom(B, H, W, C, Cout, OH, OW, KH, KW, stride, pad, 0);
-  a.dz = reinterpret_cast<const dtfe::bf16*>(dz.data_ptr());
-  a.x = reinterpret_cast<const dtfe::bf16*>(x.data_ptr());
-  a.dw = dw.data_ptr<float>();
-  a.db = ptr_or_null<float>(db);
+  a.dz = t.in<dtfe::bf16>(dz, "dz", at_least(ndz));
+  a.x = t.in<dtfe::bf16>(x, "x", at_least(nx));
+  a.dw = t.out<float>(dw, "dw", at_least(nw));
+  a.db = t.out<float>(db, "db", at_least(Cout));
   a.scale = (float)scale;
-  dtfe::launch_conv_wgrad(a, cur_stream());
+  dtfe::launch_conv_wgrad(a, t.stream());
 }
 
 // 2x2 un-pool of a pooled fp32 gradient (argmax routing) and the [O][T][C] -> [C][T][O] weight
 // transpose: the two data movers of the fp32 CNN step (conv_f32.hip)
 void unpool_f32(const Tensor& g, const Tensor& argmax, const Tensor& out, int64_t B, int64_t PH, int64_t PW,
                 int64_t C) {
-  check_cuda(g, "g");
-  TORCH_CHECK(g.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat && argmax.scalar_type() == at::kByte &&
-                  g.numel() == B * PH * PW * C && argmax.numel() == g.numel() && out.numel() == 4 * g.numel(),
-              "unpool_f32: fp32 g [B][PH][PW][C], uint8 argmax, fp32 out [B][2PH][2PW][C]");
-  dtfe::launch_unpool_f32(g.data_ptr<float>(), argmax.data_ptr<uint8_t>(), out.data_ptr<float>(), (int)B, (int)PH,
-                          (int)PW, (int)C, cur_stream());
+  const TensorArgs t("unpool_f32", g, "g");
+  const int64_t n = B * PH * PW * C;  // g [B][PH][PW][C], argmax alike, out [B][2PH][2PW][C]
+  dtfe::launch_unpool_f32(t.in<float>(g, "g", exactly(n)), t.in<uint8_t>(argmax, "argmax", exactly(n)),
+                          t.out<float>(out, "out", exactly(4 * n)), (int)B, (int)PH, (int)PW, (int)C, t.stream());
 }
 
 // MNIST conv1 weight gradient at fp32 from the pooled gradient (conv_f32.hip); false: shape not covered
 bool conv1_wgrad_pooled_f32(const Tensor& dp, const Tensor& argmax, const Tensor& x, const Tensor& dw,
                             const optional<Tensor>& db, const Tensor& ws, int64_t B, int64_t H, int64_t W, int64_t K,
                             double scale) {
-  check_cuda(dp, "dp");
-  TORCH_CHECK(dp.scalar_type() == at::kFloat && x.scalar_type() == at::kFloat && dw.scalar_type() == at::kFloat &&
-                  argmax.scalar_type() == at::kByte && ws.scalar_type() == at::kFloat,
-              "conv1_wgrad_pooled_f32: fp32 dp / x / dw / ws, uint8 argmax");
-  TORCH_CHECK(dp.is_contiguous() && argmax.is_contiguous() && x.is_contiguous() && dp.numel() == B * (H / 2) * (W / 2) * 32 &&
-                  argmax.numel() == dp.numel() && x.numel() == B * H * W && dw.numel() == 32 * K * K &&
-                  (!db.has_value() || !db->defined() || db->numel() == 32),
-              "conv1_wgrad_pooled_f32: dp [B][H/2][W/2][32], x [B][H][W][1], dw [32][K][K][1], db [32]");
+  const TensorArgs t("conv1_wgrad_pooled_f32", dp, "dp");
+  const int64_t np = B * (H / 2) * (W / 2) * 32;  // dp [B][H/2][W/2][32], x [B][H][W][1], dw [32][K][K][1], db [32]
   const dtfe::ConvGeom g = geom(B, H, W, 1, 32, H, W, K, K, 1, K / 2, 0);
-  return dtfe::launch_conv1_wgrad_pooled_f32(dp.data_ptr<float>(), argmax.data_ptr<uint8_t>(), x.data_ptr<float>(),
-                                             dw.data_ptr<float>(), ptr_or_null<float>(db), ws.data_ptr<float>(),
-                                             ws.numel(), g, (float)scale, cur_stream());
+  return dtfe::launch_conv1_wgrad_pooled_f32(t.in<float>(dp, "dp", exactly(np)), t.in<uint8_t>(argmax, "argmax", exactly(np)),
+                                             t.in<float>(x, "x", exactly(B * H * W)), t.out<float>(dw, "dw", exactly(32 * K * K)),
+                                             t.out<float>(db, "db", exactly(32)), t.out<float>(ws, "ws", at_least(0)),
+                                             ws.numel(), g, (float)scale, t.stream());
 }
 
 void transpose_taps_f32(const Tensor& in, const Tensor& out, int64_t O, int64_t T, int64_t C) {
-  check_cuda(in, "in");
-  TORCH_CHECK(in.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat && in.numel() == O * T * C &&
-                  out.numel() == in.numel() && in.is_contiguous() && out.is_contiguous(), "transpose_taps_f32: shapes");
-  dtfe::launch_transpose_taps_f32(in.data_ptr<float>(), out.data_ptr<float>(), (int)O, (int)T, (int)C, cur_stream());
+  const TensorArgs t("transpose_taps_f32", in, "in");
+  dtfe::launch_transpose_taps_f32(t.in<float>(in, "in", exactly(O * T * C)), t.out<float>(out, "out", exactly(O * T * C)),
+                                  (int)O, (int)T, (int)C, t.stream());
 }
 
 // ------------------------------------------------------------------- head
@@ -532,92 +487,80 @@ void transpose_taps_f32(const Tensor& in, const Tensor& out, int64_t O, int64_t 
 bool head_xent_f32(const Tensor& h, const Tensor& w, const optional<Tensor>& b, const Tensor& labels, const Tensor& dz,
                    const Tensor& dl, const Tensor& loss_sum, const Tensor& correct, const optional<Tensor>& logits,
                    double scale, double inv_keep, const optional<Tensor>& step_counter) {
-  check_cuda(h, "h");
-  TORCH_CHECK(h.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat && dz.scalar_type() == at::kFloat &&
-                  dl.scalar_type() == at::kFloat && labels.scalar_type() == at::kInt && h.dim() == 2 && w.dim() == 2 &&
-                  h.is_contiguous() && w.is_contiguous() && dz.is_contiguous() && dl.is_contiguous(),
-              "head_xent_f32: fp32 h [B][K], W [NC][K], dz, dl; int32 labels");
+  const TensorArgs t("head_xent_f32", h, "h");
+  TORCH_CHECK(h.dim() == 2 && w.dim() == 2 && w.size(1) == h.size(1), "head_xent_f32: fp32 h [B][K], W [NC][K]");
   dtfe::HeadF32Args a{};
   a.B = (int)h.size(0); a.K = (int)h.size(1); a.NC = (int)w.size(0);
-  TORCH_CHECK(w.size(1) == a.K && dz.numel() == h.numel() && dl.numel() == (int64_t)a.B * a.NC && labels.numel() >= a.B,
-              "head_xent_f32: shapes");
-  a.h = h.data_ptr<float>(); a.w = w.data_ptr<float>(); a.b = ptr_or_null<float>(b);
-  a.labels = labels.data_ptr<int32_t>();
+  const int64_t nl = (int64_t)a.B * a.NC;
+  a.h = t.in<float>(h, "h", exactly(h.numel())); a.w = t.in<float>(w, "w", exactly(w.numel()));
+  a.b = t.in<float>(b, "b", at_least(a.NC));
+  a.labels = t.in<int32_t>(labels, "labels", at_least(a.B));
   a.scale = (float)scale; a.inv_keep = (float)inv_keep;
-  a.dz = dz.data_ptr<float>(); a.dl = dl.data_ptr<float>();
-  a.logits_out = ptr_or_null<float>(logits);
-  TORCH_CHECK(!a.logits_out || logits->numel() == dl.numel(), "head_xent_f32: logits [B][NC]");
-  a.loss_sum = loss_sum.data_ptr<float>(); a.correct = correct.data_ptr<int32_t>();
-  a.step_counter = nullptr;
-  if (step_counter.has_value() && step_counter->defined()) {
-    TORCH_CHECK(step_counter->scalar_type() == at::kLong && step_counter->is_cuda(), "head_xent_f32: int64 step_counter");
-    a.step_counter = step_counter->data_ptr<int64_t>();
-  }
-  return dtfe::launch_head_xent_f32(a, cur_stream());
+  a.dz = t.out<float>(dz, "dz", exactly(h.numel())); a.dl = t.out<float>(dl, "dl", exactly(nl));
+  a.logits_out = t.out<float>(logits, "logits", exactly(nl));
+  a.loss_sum = t.out<float>(loss_sum, "loss_sum", at_least(1)); a.correct = t.out<int32_t>(correct, "correct", at_least(1));
+  a.step_counter = t.out<int64_t>(step_counter, "step_counter", at_least(1));
+  return dtfe::launch_head_xent_f32(a, t.stream());
 }
 
 void head_xent(const Tensor& h, const Tensor& w, const optional<Tensor>& b, const Tensor& labels, const Tensor& dz,
                const Tensor& dl, const optional<Tensor>& loss_sum, const optional<Tensor>& correct,
                const optional<Tensor>& logits, double scale, double inv_keep, const optional<Tensor>& step_counter,
                const optional<Tensor>& parts) {
-  check_cuda(h, "h");
-  TORCH_CHECK(dl.scalar_type() == at::kBFloat16 && dl.dim() == 2, "head_xent: dl must be bf16 [B][ld]");
+  const TensorArgs t("head_xent", h, "h");
+  TORCH_CHECK(h.dim() == 2 && h.size(1) >= 1 && dl.dim() == 2, "head_xent: bf16 h [B][K], dl [B][ld]");
   dtfe::HeadArgs a{};
   a.B = (int)h.size(0); a.K = (int)h.size(1); a.NC = (int)(w.numel() / a.K);
   TORCH_CHECK(dl.size(1) >= a.NC && dl.size(1) <= 64, "head_xent: dl row must hold NC classes");
-  a.h = reinterpret_cast<const dtfe::bf16*>(h.data_ptr());
-  a.w = reinterpret_cast<const dtfe::bf16*>(w.data_ptr());
-  a.b = ptr_or_null<float>(b);
-  a.labels = labels.data_ptr<int32_t>();
+  a.h = t.in<dtfe::bf16>(h, "h", exactly(h.numel()));
+  a.w = t.in<dtfe::bf16>(w, "w", exactly((int64_t)a.NC * a.K));
+  a.b = t.in<float>(b, "b", at_least(a.NC));
+  a.labels = t.in<int32_t>(labels, "labels", at_least(a.B));
   a.scale = (float)scale; a.inv_keep = (float)inv_keep;
-  a.dz = reinterpret_cast<dtfe::bf16*>(dz.data_ptr());
-  a.dl = reinterpret_cast<dtfe::bf16*>(dl.data_ptr()); a.ld_dl = (int)dl.size(1);
-  a.loss_sum = ptr_or_null<float>(loss_sum); a.correct = ptr_or_null<int32_t>(correct);
-  a.logits_out = ptr_or_null<float>(logits);
-  if (step_counter.has_value() && step_counter->defined()) {
-    TORCH_CHECK(step_counter->scalar_type() == at::kLong && step_counter->is_cuda(), "head_xent: int64 step_counter");
-    a.step_counter = step_counter->data_ptr<int64_t>();
-  }
-  if (parts.has_value() && parts->defined()) {
-    TORCH_CHECK(parts->scalar_type() == at::kFloat && parts->is_cuda() && parts->numel() >= 2 * ((a.B + 3) / 4),
-                "head_xent: parts must be fp32 [>= 2 * ceil(B / 4)]");
-    a.parts = parts->data_ptr<float>();
-  }
-  dtfe::launch_head_xent(a, cur_stream());
+  a.dz = t.out<dtfe::bf16>(dz, "dz", at_least(h.numel()));
+  a.dl = t.out<dtfe::bf16>(dl, "dl", at_least(a.B * dl.size(1))); a.ld_dl = (int)dl.size(1);
+  a.loss_sum = t.out<float>(loss_sum, "loss_sum", at_least(1)); a.correct = t.out<int32_t>(correct, "correct", at_least(1));
+  a.logits_out = t.out<float>(logits, "logits", at_least((int64_t)a.B * a.NC));
+  a.step_counter = t.out<int64_t>(step_counter, "step_counter", at_least(1));
+  a.parts = t.out<float>(parts, "parts", at_least(2 * ((a.B + 3) / 4)));  // [>= 2 * ceil(B / 4)]
+  dtfe::launch_head_xent(a, t.stream());
 }
 
 void head_wgrad(const Tensor& dl, const Tensor& h, const Tensor& dw, const optional<Tensor>& db, int64_t nc,
                 double scale, const optional<Tensor>& parts, const optional<Tensor>& loss_sum,
                 const optional<Tensor>& correct, const GroupArg& group) {
-  check_cuda(h, "h");
-  TORCH_CHECK(dl.scalar_type() == at::kBFloat16 && h.scalar_type() == at::kBFloat16 && dl.dim() == 2 && h.dim() == 2,
-              "head_wgrad: bf16 dl [B][ld] and h [B][K]");
-  TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.dim() == 2 && dw.size(0) == nc && dw.stride(1) == 1,
-              "head_wgrad: fp32 dw [NC][>=K]");
-  TORCH_CHECK(dl.size(0) == h.size(0) && dl.stride(1) == 1 && h.stride(1) == 1 && dl.size(1) >= nc,
-              "head_wgrad: batch / layout mismatch");
+  const TensorArgs t("head_wgrad", h, "h");
+  TORCH_CHECK(dl.dim() == 2 && h.dim() == 2, "head_wgrad: bf16 dl [B][ld] and h [B][K]");
+  TORCH_CHECK(dw.dim() == 2 && dw.size(0) == nc, "head_wgrad: fp32 dw [NC][>=K]");
+  TORCH_CHECK(dl.size(0) == h.size(0) && dl.size(1) >= nc, "head_wgrad: batch / layout mismatch");
   dtfe::HeadWgradArgs a{};
   a.B = (int)h.size(0); a.K = (int)h.size(1); a.NC = (int)nc;
   TORCH_CHECK(dw.size(1) >= a.K, "head_wgrad: dw rows shorter than K");
-  a.dl = reinterpret_cast<const dtfe::bf16*>(dl.data_ptr()); a.ld_dl = (int)dl.stride(0);
-  a.h = reinterpret_cast<const dtfe::bf16*>(h.data_ptr()); a.ldh = (int)h.stride(0);
-  a.dw = dw.data_ptr<float>(); a.ldw = (int)dw.stride(0);
-  if (db.has_value() && db->defined()) {
-    TORCH_CHECK(db->scalar_type() == at::kFloat && db->numel() >= nc, "head_wgrad: fp32 db [NC]");
-    a.db = db->data_ptr<float>();
-  }
+  a.ld_dl = (int)dl.stride(0); a.ldh = (int)h.stride(0); a.ldw = (int)dw.stride(0);
+  // the kernels read whole 16-B chunks: the first 16 columns of every dl row, K (% 8 == 0) of every h row
+  a.dl = t.in<dtfe::bf16>(dl, "dl", spans((int64_t)(a.B - 1) * a.ld_dl + 16));
+  a.h = t.in<dtfe::bf16>(h, "h", spans((int64_t)(a.B - 1) * a.ldh + a.K));
+  a.dw = t.out<float>(dw, "dw", spans((nc - 1) * a.ldw + a.K));
+  a.db = t.out<float>(db, "db", at_least(nc));
   a.scale = (float)scale;
-  if (parts.has_value() && parts->defined()) {
-    TORCH_CHECK(parts->scalar_type() == at::kFloat && parts->is_cuda() && parts->numel() >= 2 * ((a.B + 3) / 4),
-                "head_wgrad: parts must be fp32 [>= 2 * ceil(B / 4)] (head_xent's)");
-    TORCH_CHECK(loss_sum.has_value() && loss_sum->scalar_type() == at::kFloat && correct.has_value() &&
-                correct->scalar_type() == at::kInt, "head_wgrad: parts need fp32 loss_sum and int32 correct");
-    a.parts = parts->data_ptr<float>(); a.nparts = (a.B + 3) / 4;
-    a.loss_sum = loss_sum->data_ptr<float>(); a.correct = correct->data_ptr<int32_t>();
+  if (has(parts)) {
+    TORCH_CHECK(has(loss_sum) && has(correct), "head_wgrad: parts need fp32 loss_sum and int32 correct");
+    a.nparts = (a.B + 3) / 4;
+    a.parts = t.in<float>(parts, "parts (head_xent's)", at_least(2 * a.nparts));
+    a.loss_sum = t.out<float>(loss_sum, "loss_sum", at_least(1));
+    a.correct = t.out<int32_t>(correct, "correct", at_least(1));
   }
   auto add = [&](dtfe::GemmGroup& g) { return dtfe::gemm_group_add_head(g, a); };
   if (group.has_value() && (*group)->join(add, h, dl, dw, db, parts, loss_sum, correct)) return;
-  dtfe::launch_head_wgrad(a, cur_stream());
+  dtfe::launch_head_wgrad(a, t.stream());
+}
+
+// an optional tensor of a bound optimizer: checked, and held by the state for as long as its pointer is
+template <typename T>
+T* held_out(OptStateObj& o, const TensorArgs& t, const optional<Tensor>& x, const char* name, dtfe::Extent e) {
+  T* p = t.out<T>(x, name, e);
+  if (p) o.held.push_back(*x);
+  return p;
 }
 
 }  // namespace
@@ -632,46 +575,33 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
                          bool decay, optional<Tensor> ema, double ema_decay, bool ema_num_updates,
                          optional<Tensor> ema_out, optional<Tensor> seg_lr) {
   TORCH_CHECK(kind >= dtfe::OPT_SGD && kind <= dtfe::OPT_RMSPROP, "OptState: kind is 0 (sgd) .. 3 (rmsprop)");
-  check_cuda(p, "p");
-  TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous(), "OptState: p is contiguous float32");
+  const TensorArgs t("OptState", p, "p");
+  auto& a = args;
+  a.kind = (int)kind;
+  a.p = t.out<float>(p, "p", exactly(p.numel()));
   dev = p.get_device();
   numel = p.numel();
   held.push_back(p);
-  // an optional device tensor of the state: null when absent, else checked, held and its address
-  auto bind = [&](const optional<Tensor>& t, const char* name, bool dtype_ok, const char* dtype, int64_t least,
-                  bool exact) -> void* {
-    if (!t.has_value() || !t->defined()) return nullptr;
-    TORCH_CHECK(t->is_cuda() && t->get_device() == dev, "OptState: ", name, " is not on p's GPU");
-    TORCH_CHECK(dtype_ok && t->is_contiguous() && (exact ? t->numel() == least : t->numel() >= least), "OptState: ",
-                name, " is contiguous ", dtype, " with ", exact ? "" : "at least ", least, " elements");
-    held.push_back(*t);
-    return t->data_ptr();
-  };
-  auto is = [](const optional<Tensor>& t, at::ScalarType st) {
-    return t.has_value() && t->defined() && t->scalar_type() == st;
-  };
-  auto& a = args;
-  a.kind = (int)kind;
-  a.p = p.data_ptr<float>();
-  a.s1 = (float*)bind(s1, "s1", is(s1, at::kFloat), "float32", numel, true);
-  a.s2 = (float*)bind(s2, "s2", is(s2, at::kFloat), "float32", numel, true);
+  a.s1 = held_out<float>(*this, t, s1, "s1", exactly(numel));
+  a.s2 = held_out<float>(*this, t, s2, "s2", exactly(numel));
   a.beta1 = (float)beta1; a.beta2 = (float)beta2; a.eps = (float)eps; a.momentum = (float)momentum; a.rho = (float)rho;
-  a.beta_pow = (float*)bind(beta_pow, "beta_pow", is(beta_pow, at::kFloat), "float32", 2, false);
-  a.global_step = (int32_t*)bind(global_step, "global_step", is(global_step, at::kInt), "int32", 1, false);
-  a.done_counter = (uint32_t*)bind(done, "done", done.element_size() == 4, "4-byte", 1, false);
+  a.beta_pow = held_out<float>(*this, t, beta_pow, "beta_pow", at_least(2));
+  a.global_step = held_out<int32_t>(*this, t, global_step, "global_step", at_least(1));
+  a.done_counter = held_out<uint32_t>(*this, t, done, "done", at_least(1));
+  TORCH_CHECK(a.done_counter, "OptState: done is required");
   if (kind == dtfe::OPT_ADAM) TORCH_CHECK(a.beta_pow && a.s1 && a.s2, "OptState: adam needs slots and beta powers");
   if (kind == dtfe::OPT_RMSPROP) TORCH_CHECK(a.s1 && a.s2, "OptState: rmsprop needs slots");
   if (kind == dtfe::OPT_MOMENTUM) TORCH_CHECK(a.s1, "OptState: momentum needs a slot");
-  a.sched = (const dtfe::LrSchedule*)bind(sched, "sched (the blob of lr_schedule_pack)", is(sched, at::kByte), "uint8",
-                                          (int64_t)sizeof(dtfe::LrSchedule), true);
+  a.sched = reinterpret_cast<const dtfe::LrSchedule*>(held_out<uint8_t>(
+      *this, t, sched, "sched (the blob of lr_schedule_pack)", exactly((int64_t)sizeof(dtfe::LrSchedule))));
   TORCH_CHECK(!a.sched || a.global_step, "OptState: a learning-rate schedule needs a global_step");
-  a.lr_out = (float*)bind(lr_out, "lr_out", is(lr_out, at::kFloat), "float32", 1, false);
+  a.lr_out = held_out<float>(*this, t, lr_out, "lr_out", at_least(1));
   TORCH_CHECK(!nesterov || kind == dtfe::OPT_MOMENTUM, "OptState: nesterov is for the momentum optimizer");
   a.nesterov = nesterov ? 1 : 0;
   a.decay = decay ? 1 : 0;
   // the shadow buffer of an exponential moving average: full size, p's offsets
-  a.ema = (float*)bind(ema, "ema", is(ema, at::kFloat), "float32", numel, true);
-  a.ema_out = (float*)bind(ema_out, "ema_out", is(ema_out, at::kFloat), "float32", 1, false);
+  a.ema = held_out<float>(*this, t, ema, "ema", exactly(numel));
+  a.ema_out = held_out<float>(*this, t, ema_out, "ema_out", at_least(1));
   if (a.ema) {
     TORCH_CHECK(a.ema != a.p, "OptState: ema is a buffer of its own, not p");
     TORCH_CHECK(ema_decay >= 0.0 && (float)ema_decay < 1.f, "OptState: ema_decay lies in [0, 1), got ", ema_decay);
@@ -691,12 +621,12 @@ OptStateObj::OptStateObj(int64_t kind, Tensor p, optional<Tensor> s1, optional<T
   const Tensor S = table(segs_t, "segs", 6), W = table(work_t, "work", 7);
   const int64_t ns = S.size(0), nw = W.size(0);
   // a factor of the rate per segment (the trust ratios of ops.layer_trust): one float for every segment
-  a.seg_lr = (const float*)bind(seg_lr, "seg_lr", is(seg_lr, at::kFloat), "float32", ns, false);
+  a.seg_lr = held_out<float>(*this, t, seg_lr, "seg_lr", at_least(ns));
   TORCH_CHECK(!a.seg_lr || kind == dtfe::OPT_MOMENTUM, "OptState: seg_lr (a per-segment rate) is for the momentum "
               "optimizer, not kind ", kind);
   TORCH_CHECK(nw <= INT32_MAX, "OptState: work has too many items");
   Tensor D;
-  if (wd.has_value() && wd->defined()) {
+  if (has(wd)) {
     TORCH_CHECK(wd->device().is_cpu() && wd->scalar_type() == at::kFloat && wd->dim() == 1 && wd->size(0) == ns,
                 "OptState: wd is a CPU float32 [nseg] vector");
     D = wd->contiguous();
@@ -750,17 +680,8 @@ namespace {
 using OptStateArg = c10::intrusive_ptr<OptStateObj>;
 
 void epoch_signal(const Tensor& ctr) {
-  check_cuda(ctr, "ctr");
-  TORCH_CHECK(ctr.scalar_type() == at::kInt && ctr.numel() >= 1, "epoch_signal: int32 counter");
-  dtfe::launch_epoch_signal(ctr.data_ptr<int>(), cur_stream());
-}
-
-// the device scalar of a global-norm clip (grad_sumsq's out[1:]) multiplied into gscale; null when not given
-const float* clip_scale_ptr(const optional<Tensor>& t) {
-  if (!t.has_value() || !t->defined()) return nullptr;
-  check_cuda(*t, "clip_scale");
-  TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() >= 1, "apply_gradients: clip_scale is a float32 scalar");
-  return t->data_ptr<float>();
+  const TensorArgs t("epoch_signal", ctr, "ctr");
+  dtfe::launch_epoch_signal(t.out<int32_t>(ctr, "ctr", at_least(1)), t.stream());
 }
 
 // sum of squares of (gscale * g) over the plan's chunks -> out[0] = norm, out[1] = clip_norm / max(norm, clip_norm).
@@ -769,34 +690,23 @@ const float* clip_scale_ptr(const optional<Tensor>& t) {
 void grad_sumsq(const optional<Tensor>& g, const optional<Tensor>& g16, double gscale, double clip_norm,
                 const Tensor& plan, const Tensor& partials, const Tensor& ticket, const Tensor& out,
                 int64_t max_blocks) {
-  check_cuda(plan, "plan"); check_cuda(partials, "partials"); check_cuda(ticket, "ticket"); check_cuda(out, "out");
+  const TensorArgs t("grad_sumsq", plan, "plan");
   dtfe::GradNormArgs a{};
-  if (g.has_value() && g->defined()) {
-    check_cuda(*g, "g");
-    TORCH_CHECK(g->scalar_type() == at::kFloat && g->is_contiguous(), "grad_sumsq: g is contiguous float32");
-    a.g = g->data_ptr<float>();
-  }
-  if (g16.has_value() && g16->defined()) {
-    check_cuda(*g16, "g16");
-    TORCH_CHECK(g16->scalar_type() == at::kBFloat16 && g16->is_contiguous(), "grad_sumsq: g16 is contiguous bfloat16");
-    a.g16 = reinterpret_cast<const dtfe::bf16*>(g16->data_ptr());
-  }
+  // (the plan's offsets are the caller's: ops.grad_norm_plan builds it from the buffer it is used on)
+  a.g = t.in<float>(g, "g", at_least(0));
+  a.g16 = t.in<dtfe::bf16>(g16, "g16", at_least(0));
   TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "grad_sumsq: exactly one of g / g16");
-  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 2,
-              "grad_sumsq: plan is a contiguous int64 [nchunk, 2] table");
+  TORCH_CHECK(plan.dim() == 2 && plan.size(1) == 2, "grad_sumsq: plan is a contiguous int64 [nchunk, 2] table");
   static_assert(sizeof(dtfe::GradChunk) == 2 * sizeof(int64_t), "plan rows are GradChunk");
-  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.numel() >= plan.size(0),
-              "grad_sumsq: one float32 partial per chunk");
-  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "grad_sumsq: int32 ticket");
-  TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= 2, "grad_sumsq: float32 out[2]");
   TORCH_CHECK(clip_norm >= 0 && max_blocks >= 0, "grad_sumsq: clip_norm and max_blocks are >= 0");
   a.gscale = (float)gscale; a.clip_norm = (float)clip_norm;
-  a.plan = reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()); a.nchunk = (int)plan.size(0);
-  a.partials = partials.data_ptr<float>();
-  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
-  a.out = out.data_ptr<float>();
+  a.plan = reinterpret_cast<const dtfe::GradChunk*>(t.in<int64_t>(plan, "plan", exactly(plan.numel())));
+  a.nchunk = (int)plan.size(0);
+  a.partials = t.out<float>(partials, "partials (one per chunk)", at_least(plan.size(0)));
+  a.ticket = reinterpret_cast<uint32_t*>(t.out<int32_t>(ticket, "ticket", at_least(1)));
+  a.out = t.out<float>(out, "out", at_least(2));
   a.max_blocks = (int)max_blocks;
-  dtfe::launch_grad_sumsq(a, cur_stream());
+  dtfe::launch_grad_sumsq(a, t.stream());
 }
 
 // LARS: the norms of master and gradient of every adaptive variable and from them its trust ratio (kernels/lars.h).
@@ -808,107 +718,65 @@ void layer_trust(const Tensor& p, const optional<Tensor>& g, const optional<Tens
                  const Tensor& plan, const Tensor& segs, int64_t limit, const Tensor& wd, double eeta, double eps,
                  const optional<Tensor>& clip_scale, const Tensor& partials, const Tensor& ticket, const Tensor& sums,
                  const Tensor& trust, int64_t max_blocks) {
-  check_cuda(p, "p"); check_cuda(plan, "plan"); check_cuda(segs, "segs"); check_cuda(wd, "wd");
-  check_cuda(partials, "partials"); check_cuda(ticket, "ticket"); check_cuda(sums, "sums"); check_cuda(trust, "trust");
-  for (const Tensor* t : {&plan, &segs, &wd, &partials, &ticket, &sums, &trust})
-    TORCH_CHECK(t->get_device() == p.get_device(), "layer_trust: every tensor on p's device");
+  const TensorArgs t("layer_trust", p, "p");
   TORCH_CHECK(limit >= 0, "layer_trust: limit is >= 0");
-  TORCH_CHECK(p.scalar_type() == at::kFloat && p.is_contiguous() && p.numel() >= limit,
-              "layer_trust: p is contiguous float32 and covers the plan (", limit, " elements)");
   dtfe::LarsArgs a{};
-  a.p = p.data_ptr<float>();
-  if (g.has_value() && g->defined()) {
-    check_cuda(*g, "g");
-    TORCH_CHECK(g->scalar_type() == at::kFloat && g->is_contiguous() && g->numel() >= limit &&
-                    g->get_device() == p.get_device(),
-                "layer_trust: g is contiguous float32 on p's device and covers the plan (", limit, " elements)");
-    a.g = g->data_ptr<float>();
-  }
-  if (g16.has_value() && g16->defined()) {
-    check_cuda(*g16, "g16");
-    TORCH_CHECK(g16->scalar_type() == at::kBFloat16 && g16->is_contiguous() && g16->numel() >= limit &&
-                    g16->get_device() == p.get_device(),
-                "layer_trust: g16 is contiguous bfloat16 on p's device and covers the plan (", limit, " elements)");
-    a.g16 = reinterpret_cast<const dtfe::bf16*>(g16->data_ptr());
-  }
+  a.p = t.in<float>(p, "p", at_least(limit));
+  a.g = t.in<float>(g, "g", at_least(limit));
+  a.g16 = t.in<dtfe::bf16>(g16, "g16", at_least(limit));
   TORCH_CHECK((a.g != nullptr) != (a.g16 != nullptr), "layer_trust: exactly one of g / g16");
   static_assert(sizeof(dtfe::LarsChunk) == 3 * sizeof(int64_t), "plan rows are LarsChunk");
   static_assert(sizeof(dtfe::LarsSeg) == 3 * sizeof(int32_t), "segs rows are LarsSeg");
-  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 3 &&
-                  plan.size(0) <= INT32_MAX,
+  TORCH_CHECK(plan.dim() == 2 && plan.size(1) == 3 && plan.size(0) <= INT32_MAX,
               "layer_trust: plan is a contiguous int64 [nchunk, 3] table");
-  TORCH_CHECK(segs.scalar_type() == at::kInt && segs.is_contiguous() && segs.dim() == 2 && segs.size(1) == 3,
-              "layer_trust: segs is a contiguous int32 [nadapt, 3] table");
+  TORCH_CHECK(segs.dim() == 2 && segs.size(1) == 3, "layer_trust: segs is a contiguous int32 [nadapt, 3] table");
   const int64_t nseg = wd.numel();
-  TORCH_CHECK(wd.scalar_type() == at::kFloat && wd.is_contiguous() && segs.size(0) <= nseg,
-              "layer_trust: wd is contiguous float32 [nseg], nseg at least the adaptive segments");
-  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.numel() >= 2 * plan.size(0),
-              "layer_trust: two float32 partials per chunk");
-  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "layer_trust: int32 ticket");
-  TORCH_CHECK(sums.scalar_type() == at::kFloat && sums.is_contiguous() && sums.numel() == 2 * nseg &&
-                  trust.scalar_type() == at::kFloat && trust.is_contiguous() && trust.numel() == nseg,
-              "layer_trust: float32 sums [nseg, 2] and trust [nseg]");
+  TORCH_CHECK(segs.size(0) <= nseg, "layer_trust: wd is contiguous float32 [nseg], nseg at least the adaptive segments");
   TORCH_CHECK(std::isfinite(eeta) && eeta > 0 && std::isfinite(eps) && eps >= 0 && max_blocks >= 0,
               "layer_trust: eeta > 0, eps >= 0, max_blocks >= 0");
   a.gscale = (float)gscale;
-  a.plan = reinterpret_cast<const dtfe::LarsChunk*>(plan.data_ptr()); a.nchunk = (int)plan.size(0);
-  a.segs = reinterpret_cast<const dtfe::LarsSeg*>(segs.data_ptr()); a.nadapt = (int)segs.size(0);
-  a.wd = wd.data_ptr<float>();
+  a.plan = reinterpret_cast<const dtfe::LarsChunk*>(t.in<int64_t>(plan, "plan", exactly(plan.numel())));
+  a.nchunk = (int)plan.size(0);
+  a.segs = reinterpret_cast<const dtfe::LarsSeg*>(t.in<int32_t>(segs, "segs", exactly(segs.numel())));
+  a.nadapt = (int)segs.size(0);
+  a.wd = t.in<float>(wd, "wd", exactly(nseg));
   a.eeta = (float)eeta; a.eps = (float)eps;
-  a.clip_scale = clip_scale_ptr(clip_scale);
-  a.partials = partials.data_ptr<float>();
-  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
-  a.sums = sums.data_ptr<float>();
-  a.trust = trust.data_ptr<float>();
+  a.clip_scale = t.in<float>(clip_scale, "clip_scale", at_least(1));
+  a.partials = t.out<float>(partials, "partials (two per chunk)", at_least(2 * plan.size(0)));
+  a.ticket = reinterpret_cast<uint32_t*>(t.out<int32_t>(ticket, "ticket", at_least(1)));
+  a.sums = t.out<float>(sums, "sums", exactly(2 * nseg));
+  a.trust = t.out<float>(trust, "trust", exactly(nseg));
   a.max_blocks = (int)max_blocks;
-  dtfe::launch_layer_trust(a, cur_stream());
+  dtfe::launch_layer_trust(a, t.stream());
 }
 
 // t[i] *= scale[0] over the plan's chunks (same table as grad_sumsq's)
-void scale_(const Tensor& t, const Tensor& scale, const Tensor& plan) {
-  check_cuda(t, "t"); check_cuda(scale, "scale"); check_cuda(plan, "plan");
-  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous(), "scale_: contiguous float32 tensor");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() >= 1, "scale_: float32 scalar");
-  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() && plan.dim() == 2 && plan.size(1) == 2,
-              "scale_: plan is a contiguous int64 [nchunk, 2] table");
-  dtfe::launch_scale_ranges(t.data_ptr<float>(), scale.data_ptr<float>(),
-                            reinterpret_cast<const dtfe::GradChunk*>(plan.data_ptr()), (int)plan.size(0), cur_stream());
+void scale_(const Tensor& x, const Tensor& scale, const Tensor& plan) {
+  const TensorArgs t("scale_", x, "t");
+  TORCH_CHECK(plan.dim() == 2 && plan.size(1) == 2, "scale_: plan is a contiguous int64 [nchunk, 2] table");
+  dtfe::launch_scale_ranges(t.out<float>(x, "t", at_least(0)), t.in<float>(scale, "scale", at_least(1)),
+                            reinterpret_cast<const dtfe::GradChunk*>(t.in<int64_t>(plan, "plan", exactly(plan.numel()))),
+                            (int)plan.size(0), t.stream());
 }
 
 // one chunk of an on-device evaluation pass (kernels/eval.h)
 void eval_metrics(const Tensor& logits, const Tensor& labels, int64_t k, const Tensor& state,
                   const optional<Tensor>& idx, const Tensor& ws, const Tensor& ticket) {
-  check_cuda(logits, "logits"); check_cuda(labels, "labels"); check_cuda(state, "state"); check_cuda(ws, "ws");
-  check_cuda(ticket, "ticket");
-  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.is_contiguous() && logits.dim() == 2 && logits.size(0) >= 1 &&
-                  logits.size(1) >= 1 && logits.numel() < (int64_t(1) << 31),
+  const TensorArgs t("eval_metrics", logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.numel() < (int64_t(1) << 31),
               "eval_metrics: logits are contiguous float32 [B][NC]");
   const int64_t B = logits.size(0), NC = logits.size(1);
-  TORCH_CHECK(labels.scalar_type() == at::kInt && labels.is_contiguous() && labels.numel() == B,
-              "eval_metrics: labels are contiguous int32 [B]");
   TORCH_CHECK(k >= 1 && k <= NC, "eval_metrics: 1 <= k <= NC, got k = ", k, " for ", NC, " classes");
   static_assert(sizeof(dtfe::EvalState) == dtfe::EVAL_STATE_WORDS * sizeof(int64_t), "the state is 64-bit words");
-  TORCH_CHECK(state.scalar_type() == at::kLong && state.is_contiguous() && state.numel() >= dtfe::EVAL_STATE_WORDS,
-              "eval_metrics: state is a contiguous int64 block of ", dtfe::EVAL_STATE_WORDS, " words");
-  TORCH_CHECK(ws.scalar_type() == at::kInt && ws.is_contiguous() && ws.numel() >= 2 * B,
-              "eval_metrics: the workspace holds 2 * B int32 words");
-  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() >= 1, "eval_metrics: int32 ticket");
   dtfe::EvalMetricsArgs a{};
-  if (idx.has_value() && idx->defined()) {
-    check_cuda(*idx, "idx");
-    TORCH_CHECK(idx->scalar_type() == at::kInt && idx->is_contiguous() && idx->numel() >= B &&
-                    idx->get_device() == logits.get_device(),
-                "eval_metrics: idx is contiguous int32 [B] on the logits' device");
-    a.idx = idx->data_ptr<int32_t>();
-  }
-  for (const Tensor* t : {&labels, &state, &ws, &ticket})
-    TORCH_CHECK(t->get_device() == logits.get_device(), "eval_metrics: every tensor on the logits' device");
-  a.logits = logits.data_ptr<float>(); a.labels = labels.data_ptr<int32_t>();
+  a.logits = t.in<float>(logits, "logits", exactly(B * NC));
+  a.labels = t.in<int32_t>(labels, "labels", exactly(B));
+  a.idx = t.out<int32_t>(idx, "idx", at_least(B));
   a.B = (int)B; a.NC = (int)NC; a.k = (int)k;
-  a.state = reinterpret_cast<dtfe::EvalState*>(state.data_ptr());
-  a.ws = reinterpret_cast<uint32_t*>(ws.data_ptr());
-  a.ticket = reinterpret_cast<uint32_t*>(ticket.data_ptr());
-  dtfe::launch_eval_metrics(a, cur_stream());
+  a.state = reinterpret_cast<dtfe::EvalState*>(t.out<int64_t>(state, "state", at_least(dtfe::EVAL_STATE_WORDS)));
+  a.ws = reinterpret_cast<uint32_t*>(t.out<int32_t>(ws, "ws (2 * B words)", at_least(2 * B)));
+  a.ticket = reinterpret_cast<uint32_t*>(t.out<int32_t>(ticket, "ticket", at_least(1)));
+  dtfe::launch_eval_metrics(a, t.stream());
 }
 
 // the device copy of an LrSchedule (optim.h).  kind: 0 constant, 1 piecewise, 2 linear.  The floats arrive
@@ -941,24 +809,21 @@ Tensor lr_schedule_pack(int64_t kind, at::IntArrayRef bounds, at::ArrayRef<doubl
   return host.to(device_like.device());
 }
 
-// one launch of a bound optimizer: its template plus what varies, the gradient checked against it
-dtfe::OptArgs opt_launch_args(const OptStateObj& o, const optional<Tensor>& g, const optional<Tensor>& g16,
-                              double gscale, double lr, int64_t gs_inc, const optional<Tensor>& clip_scale) {
-  const bool f32 = g.has_value() && g->defined();
-  TORCH_CHECK(f32 != (g16.has_value() && g16->defined()), "apply_gradients: exactly one of g / g16");
-  const Tensor& t = f32 ? *g : *g16;
-  const char* name = f32 ? "g" : "g16";
-  TORCH_CHECK(t.is_cuda() && t.get_device() == o.dev, "apply_gradients: ", name, " is not on the optimizer's GPU");
-  TORCH_CHECK(t.scalar_type() == (f32 ? at::kFloat : at::kBFloat16) && t.is_contiguous() && t.numel() >= o.numel,
-              "apply_gradients: ", name, " is contiguous ", f32 ? "float32" : "bfloat16", " with at least ", o.numel,
-              " elements (p's)");
+// one launch of a bound optimizer: its template plus what varies, the gradient checked against it.
+// t: anchored on the optimizer's p (held[0]), so g / g16 / clip_scale must be on the optimizer's GPU
+dtfe::OptArgs opt_launch_args(const TensorArgs& t, const OptStateObj& o, const optional<Tensor>& g,
+                              const optional<Tensor>& g16, double gscale, double lr, int64_t gs_inc,
+                              const optional<Tensor>& clip_scale) {
+  TORCH_CHECK(has(g) != has(g16), "apply_gradients: exactly one of g / g16");
+  TORCH_CHECK(o.dev == t.device().index(), "apply_gradients: every optimizer of a group on one GPU");
   dtfe::OptArgs a = o.args;
-  if (f32) a.g = t.data_ptr<float>();
-  else a.g16 = reinterpret_cast<const dtfe::bf16*>(t.data_ptr());
+  a.g = t.in<float>(g, "g", at_least(o.numel));  // at least p's elements
+  a.g16 = t.in<dtfe::bf16>(g16, "g16", at_least(o.numel));
   a.gscale = (float)gscale;
   a.lr = (float)lr;
   a.gs_inc = (int)gs_inc;
-  a.clip_scale = clip_scale_ptr(clip_scale);
+  // the device scalar of a global-norm clip (grad_sumsq's out[1:]) multiplied into gscale; null when not given
+  a.clip_scale = t.in<float>(clip_scale, "clip_scale", at_least(1));
   return a;
 }
 
@@ -968,20 +833,18 @@ dtfe::OptArgs opt_launch_args(const OptStateObj& o, const optional<Tensor>& g, c
 void apply_gradients(const OptStateArg& o, const optional<Tensor>& g, const optional<Tensor>& g16, double gscale,
                      double lr, int64_t gs_inc, const optional<Tensor>& wait_done, const optional<Tensor>& wait_seen,
                      int64_t wait_segs, const optional<Tensor>& clip_scale) {
-  dtfe::OptArgs a = opt_launch_args(*o, g, g16, gscale, lr, gs_inc, clip_scale);
-  const bool waits = wait_done.has_value() && wait_done->defined();
-  TORCH_CHECK(waits == (wait_seen.has_value() && wait_seen->defined()) && (waits || wait_segs == 0),
+  const TensorArgs t("apply_gradients", o->held.front(), "p");
+  dtfe::OptArgs a = opt_launch_args(t, *o, g, g16, gscale, lr, gs_inc, clip_scale);
+  const bool waits = has(wait_done);
+  TORCH_CHECK(waits == has(wait_seen) && (waits || wait_segs == 0),
               "apply_gradients: wait_done, wait_seen and wait_segs go together");
   if (waits) {
-    check_cuda(*wait_done, "wait_done");
-    check_cuda(*wait_seen, "wait_seen");
-    TORCH_CHECK(wait_done->scalar_type() == at::kInt && wait_seen->scalar_type() == at::kInt &&
-                    wait_done->numel() >= 1 && wait_seen->numel() >= 1 && wait_segs >= 0 && wait_segs >> 32 == 0,
-                "apply_gradients: int32 wait counters and a 32-bit segment mask");
-    a.wait_done = wait_done->data_ptr<int>(); a.wait_seen = wait_seen->data_ptr<int>();
+    TORCH_CHECK(wait_segs >= 0 && wait_segs >> 32 == 0, "apply_gradients: int32 wait counters and a 32-bit segment mask");
+    a.wait_done = t.out<int32_t>(wait_done, "wait_done", at_least(1));
+    a.wait_seen = t.out<int32_t>(wait_seen, "wait_seen", at_least(1));
     a.wait_segs = (uint32_t)wait_segs;
   }
-  dtfe::launch_apply_gradients(a, cur_stream());
+  dtfe::launch_apply_gradients(a, t.stream());
 }
 
 // 2..OPT_GROUP_MAX optimizers of one kind over disjoint var lists of one parameter buffer (e.g. the GAN's
@@ -993,18 +856,23 @@ void apply_gradients_group(const c10::List<OptStateArg>& o, const optional<Tenso
   TORCH_CHECK(n >= 1 && n <= (size_t)dtfe::OPT_GROUP_MAX, "apply_gradients_group: 1..4 optimizers");
   TORCH_CHECK(lr.size() == n && gs_inc.size() == n && (!clip_scale.has_value() || clip_scale->size() == n),
               "apply_gradients_group: one entry per optimizer in every list");
+  const OptStateArg first = o.get(0);
+  const TensorArgs t("apply_gradients_group", first->held.front(), "p");
   dtfe::OptArgs q[dtfe::OPT_GROUP_MAX];
-  for (size_t i = 0; i < n; ++i)
-    q[i] = opt_launch_args(*o.get(i), g, g16, gscale, lr[i], gs_inc[i],
+  for (size_t i = 0; i < n; ++i) {
+    const OptStateArg oi = o.get(i);
+    q[i] = opt_launch_args(t, *oi, g, g16, gscale, lr[i], gs_inc[i],
                            clip_scale.has_value() ? clip_scale->get(i) : optional<Tensor>());
-  dtfe::launch_apply_gradients_group(q, (int)n, cur_stream());
+  }
+  dtfe::launch_apply_gradients_group(q, (int)n, t.stream());
 }
 
 // exchanges the masters of the optimizer's var list with their EMA shadows and rewrites the bf16 copies from
 // the new masters (kernels/optim.h launch_ema_swap); every pointer was checked when the state was built
 void ema_swap(const OptStateArg& o) {
   TORCH_CHECK(o->args.ema, "ema_swap: the optimizer has no EMA (OptState built without an ema buffer)");
-  dtfe::launch_ema_swap(o->args, cur_stream());
+  const TensorArgs t("ema_swap", o->held.front(), "p");
+  dtfe::launch_ema_swap(o->args, t.stream());
 }
 
 }  // namespace
@@ -1024,101 +892,70 @@ void opt_state_register() {
 namespace {
 
 // ---------------------------------------------------------- elementwise
-int data_code(const Tensor& t) {
-  if (t.scalar_type() == at::kByte) return 0;
-  if (t.scalar_type() == at::kFloat) return 1;
-  if (t.scalar_type() == at::kBFloat16) return 2;
-  TORCH_CHECK(false, "gather_rows: unsupported dtype");
-}
-
 void wgrad_tallk(const Tensor& A, int64_t lda, const Tensor& B, int64_t ldb, int64_t M, int64_t N, int64_t K,
                  const Tensor& out, int64_t ldc, const optional<Tensor>& bias, const Tensor& ws, int64_t splits,
                  double scale) {
-  check_cuda(A, "A");
-  check_cuda(B, "B");
-  check_cuda(out, "out");
-  TORCH_CHECK(A.scalar_type() == at::kFloat && B.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat &&
-                  ws.scalar_type() == at::kFloat,
-              "wgrad_tallk: fp32 operands / output / workspace");
-  TORCH_CHECK(A.numel() >= (K - 1) * lda + M && B.numel() >= (K - 1) * ldb + N && out.numel() >= (M - 1) * ldc + N,
-              "wgrad_tallk: operand / output extents");
-  TORCH_CHECK(ws.numel() >= dtfe::tallk_ws_floats((int)M, (int)N, (int)splits), "wgrad_tallk: workspace too small");
-  if (bias) TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() >= N, "wgrad_tallk: bias [N] fp32");
+  const TensorArgs t("wgrad_tallk", out, "out");
   dtfe::TallKArgs a{};
-  a.A = A.data_ptr<float>(); a.lda = (int)lda;
-  a.B = B.data_ptr<float>(); a.ldb = (int)ldb;
+  a.A = t.in<float>(A, "A", spans((K - 1) * lda + M)); a.lda = (int)lda;
+  a.B = t.in<float>(B, "B", spans((K - 1) * ldb + N)); a.ldb = (int)ldb;
   a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.out = out.data_ptr<float>(); a.ldc = (int)ldc;
-  a.bias = bias ? bias->data_ptr<float>() : nullptr;
-  a.ws = ws.data_ptr<float>(); a.splits = (int)splits;
+  a.out = t.out<float>(out, "out", spans((M - 1) * ldc + N)); a.ldc = (int)ldc;
+  a.bias = t.out<float>(bias, "bias", at_least(N));
+  a.ws = t.out<float>(ws, "ws", at_least(dtfe::tallk_ws_floats((int)M, (int)N, (int)splits))); a.splits = (int)splits;
   a.scale = (float)scale;
-  dtfe::launch_wgrad_tallk(a, cur_stream());
+  dtfe::launch_wgrad_tallk(a, t.stream());
 }
 
-dtfe::SeqStageArgs seq_stage_args(const Tensor& x, const Tensor& xh, int64_t T, int64_t I, const Tensor& ysrc,
-                                   const Tensor& ydst, at::TensorList zero) {
-  check_cuda(x, "x");
-  check_cuda(xh, "xh");
-  TORCH_CHECK(x.scalar_type() == at::kFloat && xh.scalar_type() == at::kFloat && x.is_contiguous() &&
-                  xh.is_contiguous() && xh.dim() == 3 && xh.size(0) == T && xh.size(2) > I,
+dtfe::SeqStageArgs seq_stage_args(const TensorArgs& t, const Tensor& x, const Tensor& xh, int64_t T, int64_t I,
+                                   const Tensor& ysrc, const Tensor& ydst, at::TensorList zero) {
+  TORCH_CHECK(xh.dim() == 3 && xh.size(0) == T && xh.size(2) > I && T >= 1 && I >= 1,
               "seq_stage: x f32 [B][T*I], xh f32 [T][B][ld > I] contiguous");
   const int64_t B = xh.size(1);
-  TORCH_CHECK(x.numel() == B * T * I, "seq_stage: x holds B*T*I floats");
-  TORCH_CHECK(ysrc.scalar_type() == at::kFloat && ydst.scalar_type() == at::kFloat && ysrc.is_contiguous() &&
-                  ydst.is_contiguous() && ysrc.numel() == ydst.numel() && ysrc.numel() % B == 0,
-              "seq_stage: label rows f32 [B][*], same size, contiguous");
+  TORCH_CHECK(B >= 1 && ysrc.numel() % B == 0, "seq_stage: label rows f32 [B][*], same size, contiguous");
   dtfe::SeqStageArgs a{};
-  a.x = x.data_ptr<float>();
-  a.xh = xh.data_ptr<float>();
+  a.x = t.in<float>(x, "x", exactly(B * T * I));
+  a.xh = t.out<float>(xh, "xh", exactly(xh.numel()));
   a.B = (int)B; a.T = (int)T; a.I = (int)I; a.ld = (int)xh.size(2);
-  a.ysrc = ysrc.data_ptr<float>(); a.ydst = ydst.data_ptr<float>(); a.ny = ysrc.numel();
-  TORCH_CHECK(zero.size() <= 4, "seq_stage: at most 4 zero ranges");
-  for (const Tensor& z : zero) {
-    check_cuda(z, "zero");
-    TORCH_CHECK(z.is_contiguous() && (z.numel() * z.element_size()) % 4 == 0, "seq_stage: zero ranges must be "
-                "contiguous whole 32-bit words");
-    a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
-    a.zlen[a.nz++] = z.numel() * z.element_size() / 4;
-  }
+  a.ysrc = t.in<float>(ysrc, "ysrc", exactly(ysrc.numel()));
+  a.ydst = t.out<float>(ydst, "ydst", exactly(ysrc.numel())); a.ny = ysrc.numel();
+  t.zero_ranges(zero, a.zptr, a.zlen, a.nz);
   return a;
 }
 
 void seq_stage(const Tensor& x, const Tensor& xh, int64_t T, int64_t I, const Tensor& ysrc, const Tensor& ydst,
                at::TensorList zero) {
-  dtfe::launch_seq_stage(seq_stage_args(x, xh, T, I, ysrc, ydst, zero), cur_stream());
+  const TensorArgs t("seq_stage", xh, "xh");
+  dtfe::launch_seq_stage(seq_stage_args(t, x, xh, T, I, ysrc, ydst, zero), t.stream());
 }
 
 void gather_rows(const Tensor& src, const Tensor& dst, const optional<Tensor>& idx, const optional<Tensor>& labels_src,
                  const optional<Tensor>& labels_dst, int64_t seed, const optional<Tensor>& counter,
                  const optional<Tensor>& done, at::TensorList zero, const optional<Tensor>& onehot, bool shuffle) {
-  check_cuda(src, "src");
-  TORCH_CHECK(!shuffle || !(idx.has_value() && idx->defined()), "gather_rows: shuffle samples the rows itself, it takes no idx");
-  TORCH_CHECK(!shuffle || (src.size(0) >= 1 && src.size(0) <= (int64_t(1) << 31)), "gather_rows: shuffle needs 1 <= n_rows <= 2^31");
+  const TensorArgs t("gather_rows", src, "src");
+  TORCH_CHECK(src.dim() >= 1 && src.size(0) >= 1 && dst.dim() >= 1, "gather_rows: src [n_rows][...], dst [B][...]");
+  TORCH_CHECK(!shuffle || !has(idx), "gather_rows: shuffle samples the rows itself, it takes no idx");
+  TORCH_CHECK(!shuffle || src.size(0) <= (int64_t(1) << 31), "gather_rows: shuffle needs 1 <= n_rows <= 2^31");
   dtfe::GatherArgs a{};
   a.sample = shuffle ? dtfe::SAMPLE_SHUFFLE : dtfe::SAMPLE_REPLACE;
-  if (onehot.has_value()) {
-    check_cuda(*onehot, "onehot");
-    TORCH_CHECK(onehot->scalar_type() == at::kFloat && onehot->is_contiguous() && onehot->dim() == 2 &&
-                onehot->size(0) == dst.size(0) && labels_src.has_value(),
+  const int64_t B = dst.size(0), D = src.numel() / src.size(0);
+  if (has(onehot)) {
+    TORCH_CHECK(onehot->dim() == 2 && onehot->size(0) == B && has(labels_src),
                 "gather_rows: onehot must be contiguous f32 [B][ncls] and needs labels_src");
-    a.onehot = onehot->data_ptr<float>();
+    a.onehot = t.out<float>(onehot, "onehot", exactly(onehot->numel()));
     a.ncls = (int)onehot->size(1);
   }
-  TORCH_CHECK(zero.size() <= 4, "gather_rows: at most 4 zero ranges");
-  for (const Tensor& z : zero) {
-    check_cuda(z, "zero");
-    TORCH_CHECK(z.is_contiguous() && (z.numel() * z.element_size()) % 4 == 0, "gather_rows: zero ranges must be "
-                "contiguous whole 32-bit words");
-    a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
-    a.zlen[a.nz++] = (long)(z.numel() * z.element_size() / 4);
-  }
-  a.src = src.data_ptr(); a.src_dtype = data_code(src); a.n_rows = src.size(0); a.D = (int)(src.numel() / src.size(0));
-  a.dst = dst.data_ptr(); a.dst_dtype = data_code(dst); a.B = (int)dst.size(0);
-  TORCH_CHECK(a.dst_dtype != 0, "gather_rows: dst must be f32 or bf16");
-  a.idx = ptr_or_null<int32_t>(idx);
-  a.labels_src = ptr_or_null<int32_t>(labels_src); a.labels_dst = ptr_or_null<int32_t>(labels_dst);
-  a.seed = (uint64_t)seed; a.counter = ptr_or_null<int64_t>(counter); a.done = ptr_or_null<uint32_t>(done);
-  dtfe::launch_gather_rows(a, cur_stream());
+  t.zero_ranges(zero, a.zptr, a.zlen, a.nz);
+  const dtfe::AnyPtr ps = t.any(src, "src", dtfe::ANY_DATA, exactly(src.numel()));
+  const dtfe::AnyPtr pd = t.any(dst, "dst", dtfe::F32_OR_BF16, exactly(B * D));  // f32 or bf16 rows of src's length
+  a.src = ps.p; a.src_dtype = ps.code; a.n_rows = src.size(0); a.D = (int)D;
+  a.dst = pd.p; a.dst_dtype = pd.code; a.B = (int)B;
+  a.idx = t.in<int32_t>(idx, "idx", at_least(B));
+  a.labels_src = t.in<int32_t>(labels_src, "labels_src", at_least(a.n_rows));
+  a.labels_dst = t.out<int32_t>(labels_dst, "labels_dst", at_least(B));
+  a.seed = (uint64_t)seed; a.counter = t.out<int64_t>(counter, "counter", at_least(1));
+  a.done = t.out<uint32_t>(done, "done", at_least(1));
+  dtfe::launch_gather_rows(a, t.stream());
 }
 
 // gather_rows for image rows with the input transforms in the same launch (kernels/augment.h)
@@ -1127,290 +964,245 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
                   const optional<Tensor>& labels_src, const optional<Tensor>& labels_dst, int64_t seed,
                   const optional<Tensor>& counter, const optional<Tensor>& done, at::TensorList zero,
                   const optional<Tensor>& onehot, bool shuffle) {
-  auto i32 = [](const optional<Tensor>& t, const char* name, int64_t min_numel) {
-    if (!t.has_value() || !t->defined()) return;
-    check_cuda(*t, name);
-    TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() >= min_numel, "augment_rows: ", name,
-                " must be contiguous int32 with at least ", min_numel, " elements");
-  };
-  auto given = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
-  check_cuda(src, "src");
-  check_cuda(dst, "dst");
-  TORCH_CHECK(src.get_device() == dst.get_device(), "augment_rows: src and dst on one device");
-  TORCH_CHECK(src.is_contiguous() && dst.is_contiguous(), "augment_rows: src and dst must be contiguous");
-  TORCH_CHECK(src.scalar_type() == at::kByte || src.scalar_type() == at::kFloat, "augment_rows: src must be uint8 or f32");
-  TORCH_CHECK(dst.scalar_type() == at::kFloat || dst.scalar_type() == at::kBFloat16,
-              "augment_rows: dst must be f32 or bf16");
+  const TensorArgs t("augment_rows", src, "src");
   TORCH_CHECK(H >= 1 && W >= 1 && C >= 1 && H * W * C < (int64_t(1) << 31), "augment_rows: bad image shape");
   const int64_t D = H * W * C;
   TORCH_CHECK(src.dim() == 2 && src.size(0) >= 1 && src.size(0) < (int64_t(1) << 31) && src.size(1) == D,
               "augment_rows: src must be [n_rows][H*W*C]");
-  TORCH_CHECK(dst.dim() >= 1 && dst.size(0) >= 1 && dst.size(0) < (int64_t(1) << 31) && dst.numel() == dst.size(0) * D,
-              "augment_rows: dst must hold [B][H][W][C]");
+  TORCH_CHECK(dst.dim() >= 1 && dst.size(0) >= 1 && dst.size(0) < (int64_t(1) << 31), "augment_rows: dst must hold [B][H][W][C]");
   TORCH_CHECK(pad >= 0 && pad <= dtfe::AUG_MAX_PAD && pad < std::min(H, W),
               "augment_rows: 0 <= pad <= 15 and pad < min(H, W)");
-  TORCH_CHECK(given(mean) == given(inv_std), "augment_rows: mean and inv_std come together");
-  dtfe::AugmentArgs a{};
-  if (given(mean)) {
-    for (const Tensor* t : {&*mean, &*inv_std}) {
-      check_cuda(*t, "statistics");
-      TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == C,
-                  "augment_rows: mean / inv_std must be contiguous f32 [C]");
-    }
-    a.mean = mean->data_ptr<float>();
-    a.inv_std = inv_std->data_ptr<float>();
-  }
+  TORCH_CHECK(has(mean) == has(inv_std), "augment_rows: mean and inv_std come together");
   const int64_t B = dst.size(0);
-  i32(idx, "idx", B);
-  TORCH_CHECK(!shuffle || !given(idx), "augment_rows: shuffle samples the rows itself, it takes no idx");
+  dtfe::AugmentArgs a{};
+  const dtfe::AnyPtr ps = t.any(src, "src", dtfe::U8_OR_F32, exactly(src.size(0) * D));
+  const dtfe::AnyPtr pd = t.any(dst, "dst", dtfe::F32_OR_BF16, exactly(B * D));
+  a.mean = t.in<float>(mean, "mean", exactly(C));
+  a.inv_std = t.in<float>(inv_std, "inv_std", exactly(C));
+  a.idx = t.in<int32_t>(idx, "idx", at_least(B));
+  TORCH_CHECK(!shuffle || !a.idx, "augment_rows: shuffle samples the rows itself, it takes no idx");
   a.sample = shuffle ? dtfe::SAMPLE_SHUFFLE : dtfe::SAMPLE_REPLACE;
-  i32(labels_src, "labels_src", src.size(0));
-  i32(labels_dst, "labels_dst", B);
-  TORCH_CHECK(!given(labels_dst) || given(labels_src), "augment_rows: labels_dst needs labels_src");
-  if (given(onehot)) {
-    check_cuda(*onehot, "onehot");
-    TORCH_CHECK(onehot->scalar_type() == at::kFloat && onehot->is_contiguous() && onehot->dim() == 2 &&
-                    onehot->size(0) == B && given(labels_src),
+  a.labels_src = t.in<int32_t>(labels_src, "labels_src", at_least(src.size(0)));
+  a.labels_dst = t.out<int32_t>(labels_dst, "labels_dst", at_least(B));
+  TORCH_CHECK(!a.labels_dst || a.labels_src, "augment_rows: labels_dst needs labels_src");
+  if (has(onehot)) {
+    TORCH_CHECK(onehot->dim() == 2 && onehot->size(0) == B && a.labels_src,
                 "augment_rows: onehot must be contiguous f32 [B][ncls] and needs labels_src");
-    a.onehot = onehot->data_ptr<float>();
+    a.onehot = t.out<float>(onehot, "onehot", exactly(onehot->numel()));
     a.ncls = (int)onehot->size(1);
   }
-  if (given(counter)) {
-    check_cuda(*counter, "counter");
-    TORCH_CHECK(counter->scalar_type() == at::kLong && counter->numel() >= 1, "augment_rows: counter must be int64");
-  }
-  if (given(done)) {
-    check_cuda(*done, "done");
-    TORCH_CHECK(done->element_size() == 4 && done->numel() >= 1, "augment_rows: done must be one 32-bit word");
-  }
-  TORCH_CHECK(zero.size() <= 4, "augment_rows: at most 4 zero ranges");
-  for (const Tensor& z : zero) {
-    check_cuda(z, "zero");
-    TORCH_CHECK(z.is_contiguous() && (z.numel() * z.element_size()) % 4 == 0, "augment_rows: zero ranges must be "
-                "contiguous whole 32-bit words");
-    a.zptr[a.nz] = reinterpret_cast<uint32_t*>(z.data_ptr());
-    a.zlen[a.nz++] = (long)(z.numel() * z.element_size() / 4);
-  }
-  a.src = src.data_ptr(); a.src_dtype = data_code(src); a.n_rows = src.size(0);
-  a.dst = dst.data_ptr(); a.dst_dtype = data_code(dst); a.B = (int)B;
+  a.counter = t.out<int64_t>(counter, "counter", at_least(1));
+  a.done = t.out<uint32_t>(done, "done", at_least(1));
+  t.zero_ranges(zero, a.zptr, a.zlen, a.nz);
+  a.src = ps.p; a.src_dtype = ps.code; a.n_rows = src.size(0);
+  a.dst = pd.p; a.dst_dtype = pd.code; a.B = (int)B;
   a.H = (int)H; a.W = (int)W; a.C = (int)C; a.pad = (int)pad; a.flip = flip ? 1 : 0;
-  a.idx = ptr_or_null<int32_t>(idx);
-  a.labels_src = ptr_or_null<int32_t>(labels_src); a.labels_dst = ptr_or_null<int32_t>(labels_dst);
-  a.seed = (uint64_t)seed; a.counter = ptr_or_null<int64_t>(counter); a.done = ptr_or_null<uint32_t>(done);
-  dtfe::launch_augment_rows(a, cur_stream());
+  a.seed = (uint64_t)seed;
+  dtfe::launch_augment_rows(a, t.stream());
 }
 
 void uniform_fill(const Tensor& out, double lo, double hi, int64_t seed, const optional<Tensor>& counter,
                   const optional<Tensor>& done, const optional<Tensor>& copy_src, const optional<Tensor>& copy_dst) {
-  check_cuda(out, "out");
+  const TensorArgs t("uniform_fill", out, "out");
   const float* cs = nullptr;
   float* cd = nullptr;
   long nc = 0;
-  if (copy_src.has_value() && copy_src->defined()) {
-    TORCH_CHECK(copy_dst.has_value() && copy_dst->defined(), "uniform_fill: copy_src without copy_dst");
-    TORCH_CHECK(copy_src->scalar_type() == at::kFloat && copy_dst->scalar_type() == at::kFloat &&
-                    copy_src->is_contiguous() && copy_dst->is_contiguous() && copy_src->numel() == copy_dst->numel() &&
-                    copy_src->numel() % 4 == 0 && ((uintptr_t)copy_src->data_ptr() & 15) == 0 &&
-                    ((uintptr_t)copy_dst->data_ptr() & 15) == 0,
-                "uniform_fill: the fused copy takes equal-size contiguous 16-B aligned fp32 tensors (numel % 4 == 0)");
-    cs = copy_src->data_ptr<float>();
-    cd = copy_dst->data_ptr<float>();
+  if (has(copy_src)) {
+    TORCH_CHECK(has(copy_dst), "uniform_fill: copy_src without copy_dst");
     nc = copy_src->numel();
+    cs = t.in<float>(copy_src, "copy_src", exactly(nc));
+    cd = t.out<float>(copy_dst, "copy_dst", exactly(nc));
+    TORCH_CHECK(nc % 4 == 0 && ((uintptr_t)cs & 15) == 0 && ((uintptr_t)cd & 15) == 0,
+                "uniform_fill: the fused copy takes equal-size contiguous 16-B aligned fp32 tensors (numel % 4 == 0)");
   }
-  dtfe::launch_uniform_fill(out.data_ptr<float>(), out.numel(), (float)lo, (float)hi, (uint64_t)seed,
-                            ptr_or_null<int64_t>(counter), ptr_or_null<uint32_t>(done), cur_stream(), cs, cd, nc);
+  dtfe::launch_uniform_fill(t.out<float>(out, "out", exactly(out.numel())), out.numel(), (float)lo, (float)hi,
+                            (uint64_t)seed, t.out<int64_t>(counter, "counter", at_least(1)),
+                            t.out<uint32_t>(done, "done", at_least(1)), t.stream(), cs, cd, nc);
 }
 
 void cast_(const Tensor& src, const Tensor& dst) {
-  check_cuda(src, "src");
-  TORCH_CHECK(src.numel() == dst.numel(), "cast: size mismatch");
-  if (src.scalar_type() == at::kFloat && dst.scalar_type() == at::kBFloat16)
-    dtfe::launch_cast_f32_bf16(src.data_ptr<float>(), reinterpret_cast<dtfe::bf16*>(dst.data_ptr()), src.numel(),
-                               cur_stream());
-  else if (src.scalar_type() == at::kBFloat16 && dst.scalar_type() == at::kFloat)
-    dtfe::launch_cast_bf16_f32(reinterpret_cast<const dtfe::bf16*>(src.data_ptr()), dst.data_ptr<float>(),
-                               src.numel(), cur_stream());
+  const TensorArgs t("cast_", src, "src");
+  const int64_t n = src.numel();
+  const dtfe::AnyPtr ps = t.any(src, "src", dtfe::F32_OR_BF16, exactly(n));
+  if (ps.f32())
+    dtfe::launch_cast_f32_bf16(static_cast<const float*>(ps.p), t.out<dtfe::bf16>(dst, "dst (f32<->bf16 only)", exactly(n)), n,
+                               t.stream());
   else
-    TORCH_CHECK(false, "cast: f32<->bf16 only");
+    dtfe::launch_cast_bf16_f32(static_cast<const dtfe::bf16*>(ps.p), t.out<float>(dst, "dst (f32<->bf16 only)", exactly(n)), n,
+                               t.stream());
 }
 
 void softmax_xent(const Tensor& logits, const optional<Tensor>& labels_i, const optional<Tensor>& labels_oh,
                   double scale, const optional<Tensor>& dlogits, const optional<Tensor>& loss_rows,
                   const optional<Tensor>& loss_sum, const optional<Tensor>& correct, const optional<Tensor>& probs) {
-  check_cuda(logits, "logits");
+  const TensorArgs t("softmax_xent", logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "softmax_xent: fp32 logits [B][NC]");
   dtfe::XentArgs a{};
   a.B = (int)logits.size(0); a.NC = (int)logits.size(1);
-  a.logits = logits.data_ptr<float>();
-  a.labels_i = ptr_or_null<int32_t>(labels_i); a.labels_oh = ptr_or_null<float>(labels_oh);
+  const int64_t n = logits.numel();
+  a.logits = t.in<float>(logits, "logits", exactly(n));
+  a.labels_i = t.in<int32_t>(labels_i, "labels_i", at_least(a.B));
+  a.labels_oh = t.in<float>(labels_oh, "labels_oh", at_least(n));
   TORCH_CHECK(a.labels_i || a.labels_oh, "softmax_xent: labels required");
   a.scale = (float)scale;
-  a.dlogits = ptr_or_null<float>(dlogits); a.loss_rows = ptr_or_null<float>(loss_rows);
-  a.loss_sum = ptr_or_null<float>(loss_sum); a.correct = ptr_or_null<int32_t>(correct);
-  a.probs = ptr_or_null<float>(probs);
-  dtfe::launch_softmax_xent(a, cur_stream());
+  a.dlogits = t.out<float>(dlogits, "dlogits", at_least(n)); a.loss_rows = t.out<float>(loss_rows, "loss_rows", at_least(a.B));
+  a.loss_sum = t.out<float>(loss_sum, "loss_sum", at_least(1)); a.correct = t.out<int32_t>(correct, "correct", at_least(1));
+  a.probs = t.out<float>(probs, "probs", at_least(n));
+  dtfe::launch_softmax_xent(a, t.stream());
 }
 
 bool dense_head(const Tensor& feat, const Tensor& w, const optional<Tensor>& bias, const Tensor& y,
                 const optional<Tensor>& logits, const optional<Tensor>& loss_sum, const optional<Tensor>& correct,
                 const Tensor& dw, const optional<Tensor>& db, const optional<Tensor>& dfeat, double scale,
                 bool w_fmajor, bool store, const optional<Tensor>& dl_out) {
-  check_cuda(feat, "feat");
-  const bool f32 = feat.scalar_type() == at::kFloat;
-  TORCH_CHECK((f32 || feat.scalar_type() == at::kBFloat16) && feat.dim() == 2 && feat.is_contiguous(),
-              "dense_head: bf16 / fp32 feat [B][F]");
+  const TensorArgs t("dense_head", feat, "feat");
+  TORCH_CHECK(feat.dim() == 2 && w.dim() == 2, "dense_head: bf16 / fp32 feat [B][F], fp32 w [NC][F] / [F][NC]");
   const int64_t B = feat.size(0), F = feat.size(1), NC = w_fmajor ? w.size(1) : w.size(0);
-  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 2 && w.numel() == NC * F, "dense_head: fp32 w [NC][F] / [F][NC]");
-  TORCH_CHECK(y.scalar_type() == at::kFloat && y.numel() == B * NC, "dense_head: fp32 one-hot y [B][NC]");
-  TORCH_CHECK(dw.scalar_type() == at::kFloat && dw.numel() == NC * F, "dense_head: fp32 dw");
-  const bool has_df = dfeat.has_value() && dfeat->defined();
-  TORCH_CHECK(!has_df || (dfeat->scalar_type() == feat.scalar_type() && dfeat->numel() == B * F && dfeat->is_contiguous()),
-              "dense_head: dfeat of feat's dtype [B][F]");
-  TORCH_CHECK(!dl_out.has_value() || !dl_out->defined() ||
-                  (dl_out->scalar_type() == at::kFloat && dl_out->numel() == B * NC && dl_out->is_contiguous()),
-              "dense_head: dl_out fp32 [B][NC]");
-  TORCH_CHECK(!logits.has_value() || !logits->defined() || logits->numel() == B * NC, "dense_head: logits");
   dtfe::DenseHeadArgs a{};
-  a.feat = feat.data_ptr();
-  a.f32 = f32 ? 1 : 0;
+  const dtfe::AnyPtr pf = t.any(feat, "feat", dtfe::F32_OR_BF16, exactly(B * F));
+  a.feat = pf.p;
+  a.f32 = pf.f32() ? 1 : 0;
   a.w_fmajor = w_fmajor ? 1 : 0;
   a.store = store ? 1 : 0;
-  a.w = w.data_ptr<float>(); a.bias = ptr_or_null<float>(bias); a.y = y.data_ptr<float>();
-  a.logits = ptr_or_null<float>(logits); a.loss_sum = ptr_or_null<float>(loss_sum);
-  a.correct = ptr_or_null<int32_t>(correct);
-  a.dw = dw.data_ptr<float>(); a.db = ptr_or_null<float>(db);
-  a.dfeat = has_df ? dfeat->data_ptr() : nullptr;
-  a.dl_out = ptr_or_null<float>(dl_out);
+  a.w = t.in<float>(w, "w", exactly(NC * F)); a.bias = t.in<float>(bias, "bias", at_least(NC));
+  a.y = t.in<float>(y, "y (one-hot)", exactly(B * NC));
+  a.logits = t.out<float>(logits, "logits", exactly(B * NC)); a.loss_sum = t.out<float>(loss_sum, "loss_sum", at_least(1));
+  a.correct = t.out<int32_t>(correct, "correct", at_least(1));
+  a.dw = t.out<float>(dw, "dw", exactly(NC * F)); a.db = t.out<float>(db, "db", at_least(NC));
+  // dfeat: feat's dtype and shape
+  a.dfeat = pf.f32() ? (void*)t.out<float>(dfeat, "dfeat", exactly(B * F)) : (void*)t.out<dtfe::bf16>(dfeat, "dfeat", exactly(B * F));
+  a.dl_out = t.out<float>(dl_out, "dl_out", exactly(B * NC));
   a.B = (int)B; a.F = (int)F; a.NC = (int)NC; a.scale = (float)scale;
-  return dtfe::launch_dense_head(a, cur_stream());
+  return dtfe::launch_dense_head(a, t.stream());
 }
 
 void gan_loss(const Tensor& d_real, const Tensor& d_fake, const Tensor& gen_loss, const Tensor& disc_loss,
               const Tensor& dz_real_disc, const Tensor& dz_fake_disc, const Tensor& dz_fake_gen, double clamp_eps) {
-  check_cuda(d_real, "d_real");
+  const TensorArgs t("gan_loss", d_real, "d_real");
+  const int64_t B = d_real.numel();
   dtfe::GanLossArgs a{};
-  a.B = (int)d_real.numel();
-  a.d_real = d_real.data_ptr<float>(); a.d_fake = d_fake.data_ptr<float>();
-  a.gen_loss = gen_loss.data_ptr<float>(); a.disc_loss = disc_loss.data_ptr<float>();
-  a.dz_real_disc = dz_real_disc.data_ptr<float>(); a.dz_fake_disc = dz_fake_disc.data_ptr<float>();
-  a.dz_fake_gen = dz_fake_gen.data_ptr<float>();
+  a.B = (int)B;
+  a.d_real = t.in<float>(d_real, "d_real", exactly(B)); a.d_fake = t.in<float>(d_fake, "d_fake", at_least(B));
+  a.gen_loss = t.out<float>(gen_loss, "gen_loss", at_least(1)); a.disc_loss = t.out<float>(disc_loss, "disc_loss", at_least(1));
+  a.dz_real_disc = t.out<float>(dz_real_disc, "dz_real_disc", at_least(B));
+  a.dz_fake_disc = t.out<float>(dz_fake_disc, "dz_fake_disc", at_least(B));
+  a.dz_fake_gen = t.out<float>(dz_fake_gen, "dz_fake_gen", at_least(B));
   a.clamp_eps = (float)clamp_eps;
-  dtfe::launch_gan_loss(a, cur_stream());
+  dtfe::launch_gan_loss(a, t.stream());
 }
 
 bool gan_disc_head(const Tensor& d1, const Tensor& w, const optional<Tensor>& b, const optional<Tensor>& p,
                    const optional<Tensor>& dlog, const optional<Tensor>& dlog_g, const Tensor& gw,
                    const optional<Tensor>& gb, const Tensor& dd1, const Tensor& ddf, const Tensor& gen_loss,
                    const Tensor& disc_loss, const Tensor& ws, double clamp_eps) {
-  check_cuda(d1, "d1");
-  TORCH_CHECK(d1.dim() == 2 && d1.size(0) % 2 == 0 && d1.scalar_type() == at::kFloat && d1.is_contiguous(),
-              "gan_disc_head: d1 f32 [2B][DH] contiguous");
-  const int B = (int)(d1.size(0) / 2), DH = (int)d1.size(1);
-  auto f32 = [](const Tensor& t, int64_t n) { return t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n; };
-  TORCH_CHECK(f32(w, DH) && f32(gw, DH) && f32(dd1, 2L * B * DH) && f32(ddf, (int64_t)B * DH) && f32(gen_loss, 1) &&
-                  f32(disc_loss, 1), "gan_disc_head: Wd2 / dWd2 [DH], dd1 [2B][DH], ddf [B][DH], scalar losses (f32)");
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= dtfe::gan_head_ws_floats(B, DH),
-              "gan_disc_head: ws needs ", dtfe::gan_head_ws_floats(B, DH), " zeroed floats");
-  auto opt_f32 = [](const optional<Tensor>& t) -> float* {
-    return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr;
-  };
+  const TensorArgs t("gan_disc_head", d1, "d1");
+  TORCH_CHECK(d1.dim() == 2 && d1.size(0) % 2 == 0, "gan_disc_head: d1 f32 [2B][DH] contiguous");
+  const int64_t B = d1.size(0) / 2, DH = d1.size(1);
   dtfe::GanHeadArgs a{};
-  a.B = B; a.DH = DH;
-  a.d1 = d1.data_ptr<float>(); a.w = w.data_ptr<float>(); a.b = opt_f32(b);
-  if (p && p->defined()) { TORCH_CHECK(f32(*p, 2L * B), "gan_disc_head: p [2B]"); a.p = p->data_ptr<float>(); }
-  if (dlog && dlog->defined()) { TORCH_CHECK(f32(*dlog, 2L * B), "gan_disc_head: dlog [2B]"); a.dlog = dlog->data_ptr<float>(); }
-  if (dlog_g && dlog_g->defined()) { TORCH_CHECK(f32(*dlog_g, B), "gan_disc_head: dlog_g [B]"); a.dlog_g = dlog_g->data_ptr<float>(); }
-  a.gw = gw.data_ptr<float>(); a.gb = opt_f32(gb);
-  a.dd1 = dd1.data_ptr<float>(); a.ddf = ddf.data_ptr<float>();
-  a.gen_loss = gen_loss.data_ptr<float>(); a.disc_loss = disc_loss.data_ptr<float>();
+  a.B = (int)B; a.DH = (int)DH;
+  a.d1 = t.in<float>(d1, "d1", exactly(2 * B * DH)); a.w = t.in<float>(w, "w (Wd2 [DH])", exactly(DH));
+  a.b = t.in<float>(b, "b", at_least(1));
+  a.p = t.out<float>(p, "p", exactly(2 * B));
+  a.dlog = t.out<float>(dlog, "dlog", exactly(2 * B));
+  a.dlog_g = t.out<float>(dlog_g, "dlog_g", exactly(B));
+  a.gw = t.out<float>(gw, "gw (dWd2 [DH])", exactly(DH)); a.gb = t.out<float>(gb, "gb", at_least(1));
+  a.dd1 = t.out<float>(dd1, "dd1", exactly(2 * B * DH)); a.ddf = t.out<float>(ddf, "ddf", exactly(B * DH));
+  a.gen_loss = t.out<float>(gen_loss, "gen_loss", exactly(1)); a.disc_loss = t.out<float>(disc_loss, "disc_loss", exactly(1));
   a.clamp_eps = (float)clamp_eps;
-  a.ws = ws.data_ptr<float>();
-  return dtfe::launch_gan_disc_head(a, cur_stream());
+  a.ws = t.out<float>(ws, "ws (zeroed, ops.gan_head_ws_floats)", at_least(dtfe::gan_head_ws_floats((int)B, (int)DH)));
+  return dtfe::launch_gan_disc_head(a, t.stream());
 }
 
 int64_t gan_head_ws_floats(int64_t B, int64_t DH) { return dtfe::gan_head_ws_floats((int)B, (int)DH); }
 
-void mse_sigmoid(const Tensor& y, const Tensor& t, const Tensor& loss, const Tensor& dz, const optional<Tensor>& ws) {
-  check_cuda(y, "y");
-  TORCH_CHECK(y.is_contiguous() && t.is_contiguous() && dz.is_contiguous() && t.numel() == y.numel() &&
-                  dz.numel() == y.numel(), "mse_sigmoid: contiguous y / t / dz of one size");
-  float* w = nullptr;
-  if (ws.has_value() && ws->defined()) {
-    TORCH_CHECK(ws->scalar_type() == at::kFloat && ws->numel() >= dtfe::MSE_WS_FLOATS && ws->is_contiguous(),
-                "mse_sigmoid: ws f32 [>= ", dtfe::MSE_WS_FLOATS, "], zero-initialised");
-    w = ws->data_ptr<float>();
-  }
-  dtfe::launch_mse_sigmoid(y.data_ptr<float>(), t.data_ptr<float>(), y.numel(), loss.data_ptr<float>(),
-                           dz.data_ptr<float>(), cur_stream(), w);
+void mse_sigmoid(const Tensor& y, const Tensor& target, const Tensor& loss, const Tensor& dz, const optional<Tensor>& ws) {
+  const TensorArgs t("mse_sigmoid", y, "y");
+  const int64_t n = y.numel();
+  // ws: zero-initialised
+  dtfe::launch_mse_sigmoid(t.in<float>(y, "y", exactly(n)), t.in<float>(target, "t", exactly(n)), n,
+                           t.out<float>(loss, "loss", at_least(1)), t.out<float>(dz, "dz", exactly(n)), t.stream(),
+                           t.out<float>(ws, "ws", at_least(dtfe::MSE_WS_FLOATS)));
 }
 
 void colsum(const Tensor& x, int64_t M, int64_t N, int64_t ld, const Tensor& db, double scale) {
-  check_cuda(x, "x");
-  dtfe::launch_colsum(x.data_ptr(), x.scalar_type() == at::kFloat, (int)M, (int)N, ld, db.data_ptr<float>(),
-                      (float)scale, cur_stream());
+  const TensorArgs t("colsum", x, "x");
+  const dtfe::AnyPtr px = t.any(x, "x", dtfe::F32_OR_BF16, spans((M - 1) * ld + N));
+  dtfe::launch_colsum(px.p, px.f32(), (int)M, (int)N, ld, t.out<float>(db, "db", at_least(N)), (float)scale, t.stream());
 }
 
 void act_grad(const Tensor& dy, const Tensor& y, const Tensor& dz, int64_t act) {
-  check_cuda(dy, "dy");
-  dtfe::launch_act_grad(dy.data_ptr<float>(), y.data_ptr<float>(), dz.data_ptr<float>(), dy.numel(), (int)act,
-                        cur_stream());
+  const TensorArgs t("act_grad", dy, "dy");
+  const int64_t n = dy.numel();
+  dtfe::launch_act_grad(t.in<float>(dy, "dy", exactly(n)), t.in<float>(y, "y", at_least(n)), t.out<float>(dz, "dz", at_least(n)),
+                        n, (int)act, t.stream());
 }
 
 void bias_act(const Tensor& x, const optional<Tensor>& bias, const Tensor& out, int64_t act, double keep,
               int64_t seed, const optional<Tensor>& counter) {
-  check_cuda(x, "x");
+  const TensorArgs t("bias_act", x, "x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(0) >= 1, "bias_act: x [M][N]");
   dtfe::BiasActArgs a{};
-  a.x = x.data_ptr<float>(); a.bias = ptr_or_null<float>(bias);
   a.M = (int)x.size(0); a.N = (int)(x.numel() / x.size(0)); a.act = (int)act;
-  a.keep = (float)keep; a.seed = (uint64_t)seed; a.counter = ptr_or_null<int64_t>(counter);
-  a.out = out.data_ptr(); a.out_f32 = out.scalar_type() == at::kFloat;
-  dtfe::launch_bias_act(a, cur_stream());
+  a.x = t.in<float>(x, "x", exactly(x.numel())); a.bias = t.in<float>(bias, "bias", at_least(a.N));
+  a.keep = (float)keep; a.seed = (uint64_t)seed; a.counter = t.in<int64_t>(counter, "counter", at_least(1));
+  const dtfe::AnyPtr po = t.any(out, "out", dtfe::F32_OR_BF16, at_least(x.numel()));
+  a.out = po.p; a.out_f32 = po.f32();
+  dtfe::launch_bias_act(a, t.stream());
 }
 
 void lstm_cell_fwd(const Tensor& gates, const Tensor& act, const optional<Tensor>& c_prev, const Tensor& c,
                    const Tensor& h_out, int64_t ld_h, double forget_bias) {
-  check_cuda(gates, "gates");
+  const TensorArgs t("lstm_cell_fwd", gates, "gates");
+  TORCH_CHECK(c.dim() == 2, "lstm_cell_fwd: c [B][H]");
   dtfe::LstmCellArgs a{};
-  a.B = (int)c.size(0); a.H = (int)c.size(1);
-  a.gates = gates.data_ptr<float>(); a.act = act.data_ptr<float>(); a.c_prev = ptr_or_null<float>(c_prev);
-  a.c = c.data_ptr<float>(); a.h_out = h_out.data_ptr<float>(); a.ld_h = ld_h;
+  const int64_t B = c.size(0), H = c.size(1);
+  a.B = (int)B; a.H = (int)H;
+  a.gates = t.in<float>(gates, "gates", at_least(4 * B * H)); a.act = t.out<float>(act, "act", at_least(4 * B * H));
+  a.c_prev = t.in<float>(c_prev, "c_prev", at_least(B * H));
+  a.c = t.out<float>(c, "c", exactly(B * H));
+  a.h_out = t.out<float>(h_out, "h_out", spans((B - 1) * ld_h + H)); a.ld_h = ld_h;
   a.forget_bias = (float)forget_bias;
-  dtfe::launch_lstm_cell_fwd(a, cur_stream());
+  dtfe::launch_lstm_cell_fwd(a, t.stream());
 }
 
 void lstm_cell_bwd(const Tensor& act, const optional<Tensor>& c_prev, const Tensor& c, const optional<Tensor>& dh,
                    const optional<Tensor>& dh2, const optional<Tensor>& dc_next, const Tensor& dgates,
                    const Tensor& dc_prev) {
-  check_cuda(act, "act");
+  const TensorArgs t("lstm_cell_bwd", act, "act");
+  TORCH_CHECK(c.dim() == 2, "lstm_cell_bwd: c [B][H]");
   dtfe::LstmCellArgs a{};
-  a.B = (int)c.size(0); a.H = (int)c.size(1);
-  a.act = act.data_ptr<float>(); a.c_prev = ptr_or_null<float>(c_prev); a.c = c.data_ptr<float>();
-  a.dh = ptr_or_null<float>(dh); a.dh2 = ptr_or_null<float>(dh2); a.dc_next = ptr_or_null<float>(dc_next);
-  a.dgates = dgates.data_ptr<float>(); a.dc_prev = dc_prev.data_ptr<float>();
-  dtfe::launch_lstm_cell_bwd(a, cur_stream());
+  const int64_t B = c.size(0), H = c.size(1), n = B * H;
+  a.B = (int)B; a.H = (int)H;
+  a.act = const_cast<float*>(t.in<float>(act, "act", at_least(4 * n)));
+  a.c_prev = t.in<float>(c_prev, "c_prev", at_least(n)); a.c = const_cast<float*>(t.in<float>(c, "c", exactly(n)));
+  a.dh = t.in<float>(dh, "dh", at_least(n)); a.dh2 = t.in<float>(dh2, "dh2", at_least(n));
+  a.dc_next = t.in<float>(dc_next, "dc_next", at_least(n));
+  a.dgates = t.out<float>(dgates, "dgates", at_least(4 * n)); a.dc_prev = t.out<float>(dc_prev, "dc_prev", at_least(n));
+  dtfe::launch_lstm_cell_bwd(a, t.stream());
 }
 
 // whole-sequence LSTM (lstm_seq.hip): returns false when the shape needs the per-step path
 bool lstm_seq_fwd(const Tensor& xh, const Tensor& K, const Tensor& bias, double forget_bias, const Tensor& act,
                   const Tensor& c, const Tensor& hT, const optional<Tensor>& xsrc, const optional<Tensor>& ysrc,
                   const optional<Tensor>& ydst, const optional<Tensor>& zero0, const optional<Tensor>& zero1) {
-  check_cuda(xh, "xh");
-  TORCH_CHECK(xh.dim() == 3 && xh.scalar_type() == at::kFloat && xh.is_contiguous(), "lstm_seq_fwd: xh [T][B][I+H] f32");
+  const TensorArgs t("lstm_seq_fwd", xh, "xh");
+  TORCH_CHECK(xh.dim() == 3 && hT.dim() == 2 && xh.size(2) > hT.size(1), "lstm_seq_fwd: xh [T][B][I+H] f32, hT [B][H]");
   dtfe::LstmSeqArgs a{};
   a.T = (int)xh.size(0); a.B = (int)xh.size(1); a.H = (int)hT.size(1); a.I = (int)xh.size(2) - a.H;
-  TORCH_CHECK(K.numel() == (int64_t)(a.I + a.H) * 4 * a.H && bias.numel() == 4 * a.H, "lstm_seq_fwd: K/bias shape");
-  TORCH_CHECK(act.numel() == (int64_t)a.T * a.B * 4 * a.H && c.numel() == (int64_t)a.T * a.B * a.H &&
-              hT.numel() == (int64_t)a.B * a.H, "lstm_seq_fwd: output shapes");
-  a.xh = xh.data_ptr<float>(); a.K = K.data_ptr<float>(); a.bias = bias.data_ptr<float>();
-  a.forget_bias = (float)forget_bias; a.act = act.data_ptr<float>(); a.c = c.data_ptr<float>();
-  a.hT = hT.data_ptr<float>();
-  if (xsrc.has_value() && xsrc->defined()) {  // seq_stage folded into the forward launch
-    TORCH_CHECK(ysrc.has_value() && ydst.has_value(), "lstm_seq_fwd: xsrc needs ysrc / ydst");
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = t.out<float>(xh, "xh", exactly(xh.numel()));
+  a.K = t.in<float>(K, "K", exactly((int64_t)(a.I + a.H) * 4 * a.H)); a.bias = t.in<float>(bias, "bias", exactly(4 * a.H));
+  a.forget_bias = (float)forget_bias;
+  a.act = t.out<float>(act, "act", exactly(TB * 4 * a.H)); a.c = t.out<float>(c, "c", exactly(TB * a.H));
+  a.hT = t.out<float>(hT, "hT", exactly((int64_t)a.B * a.H));
+  if (has(xsrc)) {  // seq_stage folded into the forward launch
+    TORCH_CHECK(has(ysrc) && has(ydst), "lstm_seq_fwd: xsrc needs ysrc / ydst");
     std::vector<Tensor> zero;
     for (const optional<Tensor>* z : {&zero0, &zero1})
-      if (z->has_value() && (*z)->defined()) zero.push_back(**z);
-    a.st = seq_stage_args(*xsrc, xh, a.T, a.I, *ysrc, *ydst, zero);
+      if (has(*z)) zero.push_back(**z);
+    a.st = seq_stage_args(t, *xsrc, xh, a.T, a.I, *ysrc, *ydst, zero);
   }
-  return dtfe::launch_lstm_seq_fwd(a, cur_stream());
+  return dtfe::launch_lstm_seq_fwd(a, t.stream());
 }
 
 int64_t lstm_status(bool reset) { return dtfe::lstm_split_status(reset); }
@@ -1419,41 +1211,52 @@ int64_t lstm_last_split() { return dtfe::lstm_last_split(); }
 
 bool lstm_seq_bwd(const Tensor& K, const Tensor& act, const Tensor& c, const Tensor& dhT, const Tensor& dg,
                   int64_t I, const optional<Tensor>& dl, const optional<Tensor>& wo) {
-  check_cuda(act, "act");
+  const TensorArgs t("lstm_seq_bwd", act, "act");
+  TORCH_CHECK(c.dim() == 3 && I >= 1, "lstm_seq_bwd: c [T][B][H]");
   dtfe::LstmSeqArgs a{};
   a.T = (int)c.size(0); a.B = (int)c.size(1); a.H = (int)c.size(2); a.I = (int)I;
-  TORCH_CHECK(K.numel() == (int64_t)(a.I + a.H) * 4 * a.H, "lstm_seq_bwd: K shape");
-  TORCH_CHECK(act.numel() == (int64_t)a.T * a.B * 4 * a.H && dg.numel() == act.numel() &&
-              dhT.numel() == (int64_t)a.B * a.H, "lstm_seq_bwd: shapes");
-  a.K = K.data_ptr<float>(); a.act = act.data_ptr<float>(); a.c = c.data_ptr<float>();
-  a.dhT = dhT.data_ptr<float>(); a.dg = dg.data_ptr<float>();
-  if (dl.has_value() && dl->defined()) {  // dh_T = dl . W_out^T formed by the kernel (the fused head's dlogits)
-    TORCH_CHECK(wo.has_value() && wo->defined() && wo->dim() == 2 && wo->size(0) == a.H && dl->dim() == 2 &&
-                    dl->size(0) == a.B && dl->size(1) == wo->size(1) && dl->is_contiguous() && wo->is_contiguous(),
-                "lstm_seq_bwd: dl [B][NC] with W_out [H][NC]");
-    a.dl = dl->data_ptr<float>(); a.wo = wo->data_ptr<float>(); a.nc = (int)wo->size(1);
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.K = t.in<float>(K, "K", exactly((int64_t)(a.I + a.H) * 4 * a.H));
+  a.act = const_cast<float*>(t.in<float>(act, "act", exactly(TB * 4 * a.H)));
+  a.c = const_cast<float*>(t.in<float>(c, "c", exactly(TB * a.H)));
+  a.dhT = t.in<float>(dhT, "dhT", exactly((int64_t)a.B * a.H)); a.dg = t.out<float>(dg, "dg", exactly(TB * 4 * a.H));
+  if (has(dl)) {  // dh_T = dl . W_out^T formed by the kernel (the fused head's dlogits)
+    TORCH_CHECK(has(wo) && wo->dim() == 2 && wo->size(0) == a.H && dl->dim() == 2 && dl->size(0) == a.B &&
+                    dl->size(1) == wo->size(1), "lstm_seq_bwd: dl [B][NC] with W_out [H][NC]");
+    a.dl = t.in<float>(dl, "dl", exactly(dl->numel())); a.wo = t.in<float>(wo, "wo", exactly(wo->numel()));
+    a.nc = (int)wo->size(1);
   }
-  return dtfe::launch_lstm_seq_bwd(a, cur_stream());
+  return dtfe::launch_lstm_seq_bwd(a, t.stream());
 }
 
-}  // namespace
-
 // ------------------------------------------------------------------- norm
-dtfe::BnArgs bn_common(const Tensor& x, const Tensor& stats, int64_t act) {
-  check_cuda(x, "x");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() >= 2, "bn: bf16 [..., C] input");
+// x: bf16 [..., C] viewed as [R][C]; stats (null: bn_infer has none): f32 [2][C]; every per-channel vector of the op is [>= C]
+dtfe::BnArgs bn_common(const TensorArgs& t, const Tensor& x, const Tensor* stats, int64_t act) {
+  TORCH_CHECK(x.dim() >= 2 && x.size(-1) >= 1, "bn: bf16 [..., C] input");
   dtfe::BnArgs a{};
   a.C = (int)x.size(-1);
   a.R = x.numel() / a.C;
-  a.x = reinterpret_cast<const dtfe::bf16*>(x.data_ptr());
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 2 * a.C, "bn: stats [2][C] fp32");
-  a.stats = stats.data_ptr<float>();
+  a.x = t.in<dtfe::bf16>(x, "x", exactly(x.numel()));
+  if (stats) a.stats = t.out<float>(*stats, "stats", exactly(2 * a.C));
   a.act = (int)act;
   return a;
 }
 
+// the option-A shortcut of bn_apply / bn_infer: res [B][RH][RW][RC] read at (y * rstride, x * rstride, c < RC)
+void bn_residual(const TensorArgs& t, dtfe::BnArgs& a, const optional<Tensor>& res, int64_t rstride, int64_t OH,
+                 int64_t OW) {
+  if (!has(res)) return;
+  TORCH_CHECK(res->dim() == 4 && rstride >= 1 && OH >= 1 && OW >= 1 && res->size(0) * OH * OW == a.R &&
+                  (OH - 1) * rstride < res->size(1) && (OW - 1) * rstride < res->size(2),
+              "bn: residual NHWC [B][> (OH - 1) * rstride][> (OW - 1) * rstride][RC] for B * OH * OW rows");
+  a.res = t.in<dtfe::bf16>(res, "res", exactly(res->numel()));
+  a.RH = (int)res->size(1); a.RW = (int)res->size(2); a.RC = (int)res->size(3);
+  a.rstride = (int)rstride; a.OH = (int)OH; a.OW = (int)OW;
+}
+
 void bn_stats(const Tensor& x, const Tensor& stats) {
-  dtfe::launch_bn_stats(bn_common(x, stats, 0), cur_stream());
+  const TensorArgs t("bn_stats", x, "x");
+  dtfe::launch_bn_stats(bn_common(t, x, &stats, 0), t.stream());
 }
 
 void bn_apply(const Tensor& x, const Tensor& stats, const Tensor& gamma, const Tensor& beta,
@@ -1461,196 +1264,198 @@ void bn_apply(const Tensor& x, const Tensor& stats, const Tensor& gamma, const T
               const optional<Tensor>& moving_var, double eps, double momentum, int64_t act,
               const optional<Tensor>& res, int64_t rstride, int64_t OH, int64_t OW, const Tensor& out,
               const optional<Tensor>& mask_out, const optional<std::vector<Tensor>>& res_bn) {
-  dtfe::BnArgs a = bn_common(x, stats, act);
+  const TensorArgs t("bn_apply", x, "x");
+  dtfe::BnArgs a = bn_common(t, x, &stats, act);
+  const auto C = at_least(a.C);
   if (res_bn.has_value() && !res_bn->empty()) {
     // [stats, gamma, beta, mean, invstd, moving_mean, moving_var] of the residual's own BatchNorm
     const auto& r = *res_bn;
-    TORCH_CHECK(r.size() == 7 && res.has_value() && res->sizes() == x.sizes(),
+    TORCH_CHECK(r.size() == 7 && has(res) && res->sizes() == x.sizes(),
                 "bn_apply: res_bn = [stats, gamma, beta, mean, invstd, moving_mean, moving_var] of a same-shape raw residual");
-    for (const auto& t : r) TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat, "bn_apply: res_bn fp32 tensors");
-    a.r_stats = r[0].data_ptr<float>(); a.r_gamma = r[1].data_ptr<float>(); a.r_beta = r[2].data_ptr<float>();
-    a.r_mean = r[3].data_ptr<float>(); a.r_invstd = r[4].data_ptr<float>();
-    a.r_moving_mean = r[5].data_ptr<float>(); a.r_moving_var = r[6].data_ptr<float>();
+    a.r_stats = t.out<float>(r[0], "res_bn[0] (stats)", at_least(2 * a.C));
+    a.r_gamma = t.in<float>(r[1], "res_bn[1] (gamma)", C); a.r_beta = t.in<float>(r[2], "res_bn[2] (beta)", C);
+    a.r_mean = t.out<float>(r[3], "res_bn[3] (mean)", C); a.r_invstd = t.out<float>(r[4], "res_bn[4] (invstd)", C);
+    a.r_moving_mean = t.out<float>(r[5], "res_bn[5] (moving_mean)", C);
+    a.r_moving_var = t.out<float>(r[6], "res_bn[6] (moving_var)", C);
   }
-  if (mask_out.has_value() && mask_out->defined()) {
-    TORCH_CHECK(mask_out->is_cuda() && mask_out->scalar_type() == at::kByte && mask_out->numel() == x.numel() / 8 &&
-                    act == 1, "bn_apply: mask_out is a uint8 [R][C/8] ReLU bit mask");
-    a.mask_out = mask_out->data_ptr<uint8_t>();
+  if (has(mask_out)) {
+    TORCH_CHECK(act == 1, "bn_apply: mask_out is a uint8 [R][C/8] ReLU bit mask");
+    a.mask_out = t.out<uint8_t>(mask_out, "mask_out", exactly(x.numel() / 8));
   }
-  a.gamma = gamma.data_ptr<float>();
-  a.beta = beta.data_ptr<float>();
-  a.mean = ptr_or_null<float>(mean);
-  a.invstd = ptr_or_null<float>(invstd);
-  a.moving_mean = ptr_or_null<float>(moving_mean);
-  a.moving_var = ptr_or_null<float>(moving_var);
+  a.gamma = t.in<float>(gamma, "gamma", C);
+  a.beta = t.in<float>(beta, "beta", C);
+  a.mean = t.out<float>(mean, "mean", C);
+  a.invstd = t.out<float>(invstd, "invstd", C);
+  a.moving_mean = t.out<float>(moving_mean, "moving_mean", C);
+  a.moving_var = t.out<float>(moving_var, "moving_var", C);
   a.eps = (float)eps; a.momentum = (float)momentum;
-  a.res = ptr_or_null<dtfe::bf16>(res);
-  if (a.res) {
-    TORCH_CHECK(res->dim() == 4, "bn_apply: residual NHWC");
-    a.RH = (int)res->size(1); a.RW = (int)res->size(2); a.RC = (int)res->size(3);
-    a.rstride = (int)rstride; a.OH = (int)OH; a.OW = (int)OW;
-  }
-  TORCH_CHECK(out.numel() == x.numel() && out.scalar_type() == at::kBFloat16, "bn_apply: out");
-  a.out = reinterpret_cast<dtfe::bf16*>(out.data_ptr());
-  dtfe::launch_bn_apply(a, cur_stream());
+  bn_residual(t, a, res, rstride, OH, OW);
+  a.out = t.out<dtfe::bf16>(out, "out", exactly(x.numel()));
+  dtfe::launch_bn_apply(a, t.stream());
 }
 
 // inference-mode BatchNorm: out = act(gamma * (x - moving_mean) * rsqrt(moving_var + eps) + beta [+ res])
 void bn_infer(const Tensor& x, const Tensor& gamma, const Tensor& beta, const Tensor& moving_mean,
               const Tensor& moving_var, double eps, int64_t act, const optional<Tensor>& res, int64_t rstride,
               int64_t OH, int64_t OW, const Tensor& out) {
-  check_cuda(x, "x");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() >= 2, "bn_infer: bf16 [..., C] input");
-  dtfe::BnArgs a{};
-  a.C = (int)x.size(-1);
-  a.R = x.numel() / a.C;
-  a.x = reinterpret_cast<const dtfe::bf16*>(x.data_ptr());
-  a.act = (int)act;
+  const TensorArgs t("bn_infer", x, "x");
+  dtfe::BnArgs a = bn_common(t, x, nullptr, act);
   a.infer = 1;
-  TORCH_CHECK(moving_mean.numel() == a.C && moving_var.numel() == a.C, "bn_infer: moving averages [C]");
-  a.gamma = gamma.data_ptr<float>();
-  a.beta = beta.data_ptr<float>();
-  a.moving_mean = moving_mean.data_ptr<float>();
-  a.moving_var = moving_var.data_ptr<float>();
+  a.gamma = t.in<float>(gamma, "gamma", at_least(a.C));
+  a.beta = t.in<float>(beta, "beta", at_least(a.C));
+  a.moving_mean = const_cast<float*>(t.in<float>(moving_mean, "moving_mean", exactly(a.C)));
+  a.moving_var = const_cast<float*>(t.in<float>(moving_var, "moving_var", exactly(a.C)));
   a.eps = (float)eps;
-  a.res = ptr_or_null<dtfe::bf16>(res);
-  if (a.res) {
-    TORCH_CHECK(res->dim() == 4, "bn_infer: residual NHWC");
-    a.RH = (int)res->size(1); a.RW = (int)res->size(2); a.RC = (int)res->size(3);
-    a.rstride = (int)rstride; a.OH = (int)OH; a.OW = (int)OW;
-  }
-  TORCH_CHECK(out.numel() == x.numel() && out.scalar_type() == at::kBFloat16, "bn_infer: out");
-  a.out = reinterpret_cast<dtfe::bf16*>(out.data_ptr());
-  dtfe::launch_bn_apply(a, cur_stream());
+  bn_residual(t, a, res, rstride, OH, OW);
+  a.out = t.out<dtfe::bf16>(out, "out", exactly(x.numel()));
+  dtfe::launch_bn_apply(a, t.stream());
 }
 
-// the backward's ReLU-mask source: the bf16 forward output, or its uint8 [R][C/8] bit mask (ReLU only)
-void set_bwd_y(dtfe::BnArgs& a, const optional<Tensor>& y, const Tensor& x) {
-  if (y.has_value() && y->defined() && y->scalar_type() == at::kByte) {
-    TORCH_CHECK(y->is_cuda() && y->numel() == x.numel() / 8 && a.act == 1, "bn_bwd: bit mask is uint8 [R][C/8], ReLU");
-    a.ymask = y->data_ptr<uint8_t>();
+// the backward's upstream gradient and ReLU-mask source: the bf16 forward output, or its uint8 [R][C/8] bit mask (ReLU only)
+void set_bwd_dy_y(const TensorArgs& t, dtfe::BnArgs& a, const Tensor& dy, const optional<Tensor>& y, const Tensor& x) {
+  a.dy = t.in<dtfe::bf16>(dy, "dy", exactly(x.numel()));
+  if (has(y) && y->scalar_type() == at::kByte) {
+    TORCH_CHECK(a.act == 1, "bn_bwd: bit mask is uint8 [R][C/8], ReLU");
+    a.ymask = t.in<uint8_t>(y, "y (bit mask)", exactly(x.numel() / 8));
     return;
   }
-  a.y = ptr_or_null<dtfe::bf16>(y);
+  a.y = t.in<dtfe::bf16>(y, "y", exactly(x.numel()));
 }
 
 void bn_bwd_stats(const Tensor& dy, const optional<Tensor>& y, const Tensor& x, const Tensor& mean,
                   const Tensor& invstd, const Tensor& stats, int64_t act, const optional<Tensor>& gamma,
                   const optional<Tensor>& beta, const optional<std::vector<Tensor>>& res_bn) {
-  dtfe::BnArgs a = bn_common(x, stats, act);
+  const TensorArgs t("bn_bwd_stats", x, "x");
+  dtfe::BnArgs a = bn_common(t, x, &stats, act);
+  const auto C = at_least(a.C);
   if (res_bn.has_value() && !res_bn->empty()) {
     // [x, mean, invstd, stats] of a projection shortcut's BN: its statistics from the same g
     const auto& r = *res_bn;
-    TORCH_CHECK(r.size() == 4 && r[0].sizes() == x.sizes() && r[0].scalar_type() == at::kBFloat16 &&
-                    r[1].scalar_type() == at::kFloat && r[2].scalar_type() == at::kFloat &&
-                    r[3].scalar_type() == at::kFloat && r[3].numel() == 2 * a.C,
-                "bn_bwd_stats: res_bn = [x bf16 (same shape), mean, invstd, stats [2][C]]");
-    a.res = reinterpret_cast<const dtfe::bf16*>(r[0].data_ptr());
-    a.r_mean = r[1].data_ptr<float>(); a.r_invstd = r[2].data_ptr<float>(); a.r_stats = r[3].data_ptr<float>();
+    TORCH_CHECK(r.size() == 4 && r[0].sizes() == x.sizes(), "bn_bwd_stats: res_bn = [x bf16 (same shape), mean, invstd, stats [2][C]]");
+    a.res = t.in<dtfe::bf16>(r[0], "res_bn[0] (x)", exactly(x.numel()));
+    a.r_mean = const_cast<float*>(t.in<float>(r[1], "res_bn[1] (mean)", C));
+    a.r_invstd = const_cast<float*>(t.in<float>(r[2], "res_bn[2] (invstd)", C));
+    a.r_stats = t.out<float>(r[3], "res_bn[3] (stats)", exactly(2 * a.C));
   }
-  a.dy = reinterpret_cast<const dtfe::bf16*>(dy.data_ptr());
-  set_bwd_y(a, y, x);
-  a.gamma = ptr_or_null<float>(gamma);
-  a.beta = ptr_or_null<float>(beta);
+  set_bwd_dy_y(t, a, dy, y, x);
+  a.gamma = t.in<float>(gamma, "gamma", C);
+  a.beta = t.in<float>(beta, "beta", C);
   TORCH_CHECK(act == 0 || a.y || a.ymask || (act == 1 && a.gamma && a.beta),
               "bn_bwd: the activation gradient needs the forward output (or, for ReLU, gamma and beta)");
-  a.mean = mean.data_ptr<float>();
-  a.invstd = invstd.data_ptr<float>();
-  dtfe::launch_bn_bwd_stats(a, cur_stream());
+  a.mean = const_cast<float*>(t.in<float>(mean, "mean", C));
+  a.invstd = const_cast<float*>(t.in<float>(invstd, "invstd", C));
+  dtfe::launch_bn_bwd_stats(a, t.stream());
 }
 
 void bn_bwd_apply(const Tensor& dy, const optional<Tensor>& y, const Tensor& x, const Tensor& mean,
                   const Tensor& invstd, const Tensor& gamma, const Tensor& stats, int64_t act, const Tensor& dx,
                   const optional<Tensor>& dres, const optional<Tensor>& dgamma, const optional<Tensor>& dbeta,
                   const optional<Tensor>& beta) {
-  dtfe::BnArgs a = bn_common(x, stats, act);
-  a.dy = reinterpret_cast<const dtfe::bf16*>(dy.data_ptr());
-  set_bwd_y(a, y, x);
-  a.beta = ptr_or_null<float>(beta);
+  const TensorArgs t("bn_bwd_apply", x, "x");
+  dtfe::BnArgs a = bn_common(t, x, &stats, act);
+  const auto C = at_least(a.C);
+  set_bwd_dy_y(t, a, dy, y, x);
+  a.beta = t.in<float>(beta, "beta", C);
   TORCH_CHECK(act == 0 || a.y || a.ymask || (act == 1 && a.beta),
               "bn_bwd: the activation gradient needs the forward output (or, for ReLU, beta)");
-  a.mean = mean.data_ptr<float>();
-  a.invstd = invstd.data_ptr<float>();
-  a.gamma = gamma.data_ptr<float>();
-  a.out = reinterpret_cast<dtfe::bf16*>(dx.data_ptr());
-  a.dres = ptr_or_null<dtfe::bf16>(dres);
-  a.dgamma = ptr_or_null<float>(dgamma);
-  a.dbeta = ptr_or_null<float>(dbeta);
-  dtfe::launch_bn_bwd_apply(a, cur_stream());
+  a.mean = const_cast<float*>(t.in<float>(mean, "mean", C));
+  a.invstd = const_cast<float*>(t.in<float>(invstd, "invstd", C));
+  a.gamma = t.in<float>(gamma, "gamma", C);
+  a.out = t.out<dtfe::bf16>(dx, "dx", exactly(x.numel()));
+  a.dres = t.out<dtfe::bf16>(dres, "dres", exactly(x.numel()));
+  a.dgamma = t.out<float>(dgamma, "dgamma", C);
+  a.dbeta = t.out<float>(dbeta, "dbeta", C);
+  dtfe::launch_bn_bwd_apply(a, t.stream());
 }
 
 void shortcut_grad_add(const Tensor& g, const Tensor& dx, int64_t stride) {
-  TORCH_CHECK(g.dim() == 4 && dx.dim() == 4, "shortcut_grad_add: NHWC tensors");
-  dtfe::launch_shortcut_grad_add(reinterpret_cast<const dtfe::bf16*>(g.data_ptr()),
-                                 reinterpret_cast<dtfe::bf16*>(dx.data_ptr()), (int)g.size(0), (int)g.size(1),
-                                 (int)g.size(2), (int)g.size(3), (int)dx.size(1), (int)dx.size(2), (int)dx.size(3),
-                                 (int)stride, cur_stream());
+  const TensorArgs t("shortcut_grad_add", g, "g");
+  // dx[b, y * stride, x * stride, c] += g[b, y, x, c] for c < XC
+  TORCH_CHECK(g.dim() == 4 && dx.dim() == 4 && stride >= 1 && g.size(0) == dx.size(0) && g.numel() > 0 &&
+                  (g.size(1) - 1) * stride < dx.size(1) && (g.size(2) - 1) * stride < dx.size(2) && dx.size(3) <= g.size(3),
+              "shortcut_grad_add: NHWC tensors g [B][OH][OW][C], dx [B][> (OH - 1) * stride][> (OW - 1) * stride][<= C]");
+  dtfe::launch_shortcut_grad_add(t.in<dtfe::bf16>(g, "g", exactly(g.numel())), t.out<dtfe::bf16>(dx, "dx", exactly(dx.numel())),
+                                 (int)g.size(0), (int)g.size(1), (int)g.size(2), (int)g.size(3), (int)dx.size(1),
+                                 (int)dx.size(2), (int)dx.size(3), (int)stride, t.stream());
 }
 
 void gap_fwd(const Tensor& x, const Tensor& y) {
+  const TensorArgs t("gap_fwd", x, "x");
   TORCH_CHECK(x.dim() == 4, "gap_fwd: NHWC input");
-  dtfe::launch_gap_fwd(reinterpret_cast<const dtfe::bf16*>(x.data_ptr()), reinterpret_cast<dtfe::bf16*>(y.data_ptr()),
-                       (int)x.size(0), (int)(x.size(1) * x.size(2)), (int)x.size(3), cur_stream());
+  dtfe::launch_gap_fwd(t.in<dtfe::bf16>(x, "x", exactly(x.numel())), t.out<dtfe::bf16>(y, "y", exactly(x.size(0) * x.size(3))),
+                       (int)x.size(0), (int)(x.size(1) * x.size(2)), (int)x.size(3), t.stream());
 }
 
 void gap_bwd(const Tensor& dy, const Tensor& dx) {
+  const TensorArgs t("gap_bwd", dx, "dx");
   TORCH_CHECK(dx.dim() == 4, "gap_bwd: NHWC output");
-  dtfe::launch_gap_bwd(reinterpret_cast<const dtfe::bf16*>(dy.data_ptr()), reinterpret_cast<dtfe::bf16*>(dx.data_ptr()),
-                       (int)dx.size(0), (int)(dx.size(1) * dx.size(2)), (int)dx.size(3), cur_stream());
+  dtfe::launch_gap_bwd(t.in<dtfe::bf16>(dy, "dy", exactly(dx.size(0) * dx.size(3))), t.out<dtfe::bf16>(dx, "dx", exactly(dx.numel())),
+                       (int)dx.size(0), (int)(dx.size(1) * dx.size(2)), (int)dx.size(3), t.stream());
+}
+
+// 3x3 / stride 2 / pad 1: x [B][H][W][C], y and am [B][ceil(H/2)][ceil(W/2)][C]
+void check_pool3(const char* op, const Tensor& x, const Tensor& y) {
+  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && y.size(0) == x.size(0) && y.size(3) == x.size(3) &&
+                  y.size(1) == (x.size(1) + 1) / 2 && y.size(2) == (x.size(2) + 1) / 2,
+              op, ": NHWC tensors [B][H][W][C] and [B][ceil(H/2)][ceil(W/2)][C]");
 }
 
 void maxpool3_fwd(const Tensor& x, const Tensor& y, const Tensor& am) {
-  TORCH_CHECK(x.dim() == 4 && y.dim() == 4, "maxpool3: NHWC tensors");
-  dtfe::launch_maxpool3_fwd(reinterpret_cast<const dtfe::bf16*>(x.data_ptr()), reinterpret_cast<dtfe::bf16*>(y.data_ptr()),
-                            am.data_ptr<uint8_t>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3),
-                            (int)y.size(1), (int)y.size(2), cur_stream());
+  const TensorArgs t("maxpool3_fwd", x, "x");
+  check_pool3("maxpool3_fwd", x, y);
+  dtfe::launch_maxpool3_fwd(t.in<dtfe::bf16>(x, "x", exactly(x.numel())), t.out<dtfe::bf16>(y, "y", exactly(y.numel())),
+                            t.out<uint8_t>(am, "am", exactly(y.numel())), (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                            (int)x.size(3), (int)y.size(1), (int)y.size(2), t.stream());
 }
 
 void pool3_bn_bwd(const Tensor& dp, const Tensor& am, const Tensor& x, const Tensor& mean, const Tensor& invstd,
                   const Tensor& gamma, const Tensor& beta, const Tensor& stats, const Tensor& dx,
                   const optional<Tensor>& dgamma, const optional<Tensor>& dbeta) {
-  TORCH_CHECK(dp.dim() == 4 && x.dim() == 4 && dx.sizes() == x.sizes() && am.sizes() == dp.sizes() &&
-                  am.scalar_type() == at::kByte && dp.scalar_type() == at::kBFloat16 &&
-                  dx.scalar_type() == at::kBFloat16 && dp.size(0) == x.size(0) && dp.size(3) == x.size(3),
+  const TensorArgs t("pool3_bn_bwd", x, "x");
+  TORCH_CHECK(dp.dim() == 4 && x.dim() == 4 && dp.size(0) == x.size(0) && dp.size(3) == x.size(3),
               "pool3_bn_bwd: dp / am [B][OH][OW][C], x / dx [B][H][W][C]");
-  dtfe::BnArgs a = bn_common(x, stats, 1);
-  a.dy = reinterpret_cast<const dtfe::bf16*>(dp.data_ptr());
-  a.mean = mean.data_ptr<float>();
-  a.invstd = invstd.data_ptr<float>();
-  a.gamma = gamma.data_ptr<float>();
-  a.beta = beta.data_ptr<float>();
-  a.out = reinterpret_cast<dtfe::bf16*>(dx.data_ptr());
-  a.dgamma = ptr_or_null<float>(dgamma);
-  a.dbeta = ptr_or_null<float>(dbeta);
-  dtfe::launch_pool3_bn_bwd(a, am.data_ptr<uint8_t>(), (int)x.size(0), (int)x.size(1), (int)x.size(2),
-                            (int)dp.size(1), (int)dp.size(2), cur_stream());
+  dtfe::BnArgs a = bn_common(t, x, &stats, 1);
+  const auto C = at_least(a.C);
+  a.dy = t.in<dtfe::bf16>(dp, "dp", exactly(dp.numel()));
+  a.mean = const_cast<float*>(t.in<float>(mean, "mean", C));
+  a.invstd = const_cast<float*>(t.in<float>(invstd, "invstd", C));
+  a.gamma = t.in<float>(gamma, "gamma", C);
+  a.beta = t.in<float>(beta, "beta", C);
+  a.out = t.out<dtfe::bf16>(dx, "dx", exactly(x.numel()));
+  a.dgamma = t.out<float>(dgamma, "dgamma", C);
+  a.dbeta = t.out<float>(dbeta, "dbeta", C);
+  dtfe::launch_pool3_bn_bwd(a, t.in<uint8_t>(am, "am", exactly(dp.numel())), (int)x.size(0), (int)x.size(1), (int)x.size(2),
+                            (int)dp.size(1), (int)dp.size(2), t.stream());
 }
 
 void bn_relu_pool3(const Tensor& x, const Tensor& stats, const Tensor& gamma, const Tensor& beta,
                    const optional<Tensor>& mean, const optional<Tensor>& invstd, const optional<Tensor>& moving_mean,
                    const optional<Tensor>& moving_var, double eps, double momentum, const Tensor& y,
                    const Tensor& am) {
-  TORCH_CHECK(x.dim() == 4 && y.dim() == 4 && am.dim() == 4, "bn_relu_pool3: NHWC tensors");
-  TORCH_CHECK(y.scalar_type() == at::kBFloat16 && am.scalar_type() == at::kByte && y.sizes() == am.sizes() &&
-                  y.size(0) == x.size(0) && y.size(3) == x.size(3) && y.size(1) == (x.size(1) + 1) / 2 &&
-                  y.size(2) == (x.size(2) + 1) / 2, "bn_relu_pool3: y bf16 / am uint8 [B][ceil(H/2)][ceil(W/2)][C]");
-  dtfe::BnArgs a = bn_common(x, stats, 1);
-  a.gamma = gamma.data_ptr<float>();
-  a.beta = beta.data_ptr<float>();
-  a.mean = ptr_or_null<float>(mean);
-  a.invstd = ptr_or_null<float>(invstd);
-  a.moving_mean = ptr_or_null<float>(moving_mean);
-  a.moving_var = ptr_or_null<float>(moving_var);
+  const TensorArgs t("bn_relu_pool3", x, "x");
+  check_pool3("bn_relu_pool3", x, y);
+  dtfe::BnArgs a = bn_common(t, x, &stats, 1);
+  const auto C = at_least(a.C);
+  a.gamma = t.in<float>(gamma, "gamma", C);
+  a.beta = t.in<float>(beta, "beta", C);
+  a.mean = t.out<float>(mean, "mean", C);
+  a.invstd = t.out<float>(invstd, "invstd", C);
+  a.moving_mean = t.out<float>(moving_mean, "moving_mean", C);
+  a.moving_var = t.out<float>(moving_var, "moving_var", C);
   a.eps = (float)eps; a.momentum = (float)momentum;
-  dtfe::launch_bn_relu_pool3(a, reinterpret_cast<dtfe::bf16*>(y.data_ptr()), am.data_ptr<uint8_t>(), (int)x.size(0),
-                             (int)x.size(1), (int)x.size(2), (int)y.size(1), (int)y.size(2), cur_stream());
+  dtfe::launch_bn_relu_pool3(a, t.out<dtfe::bf16>(y, "y", exactly(y.numel())), t.out<uint8_t>(am, "am", exactly(y.numel())),
+                             (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)y.size(1), (int)y.size(2), t.stream());
 }
 
 void maxpool3_bwd(const Tensor& dy, const Tensor& am, const Tensor& dx) {
-  dtfe::launch_maxpool3_bwd(reinterpret_cast<const dtfe::bf16*>(dy.data_ptr()), am.data_ptr<uint8_t>(),
-                            reinterpret_cast<dtfe::bf16*>(dx.data_ptr()), (int)dx.size(0), (int)dx.size(1),
-                            (int)dx.size(2), (int)dx.size(3), (int)dy.size(1), (int)dy.size(2), cur_stream());
+  const TensorArgs t("maxpool3_bwd", dx, "dx");
+  check_pool3("maxpool3_bwd", dx, dy);
+  dtfe::launch_maxpool3_bwd(t.in<dtfe::bf16>(dy, "dy", exactly(dy.numel())), t.in<uint8_t>(am, "am", exactly(dy.numel())),
+                            t.out<dtfe::bf16>(dx, "dx", exactly(dx.numel())), (int)dx.size(0), (int)dx.size(1),
+                            (int)dx.size(2), (int)dx.size(3), (int)dy.size(1), (int)dy.size(2), t.stream());
 }
+
+}  // namespace
 
 TORCH_LIBRARY(dtfe, m) {
   m.def("conv1_gather_fwd(Tensor images, Tensor labels_src, int seed, Tensor(a!) counter, Tensor(b!) done,"

@@ -8,6 +8,7 @@ MI355X replacement for TF's graph executor on the per-step hot path.
 """
 from __future__ import annotations
 
+import gc
 import os
 
 import torch
@@ -46,13 +47,25 @@ class StepGraph:
         if self._calls <= self.warmup:
             return self.fn()
         torch.cuda.synchronize()
+        # No garbage collection inside the capture: a dead reference cycle may hold an earlier captured
+        # graph (a MultiStepGraph and the closures it hands its StepGraphs form one), and a collection
+        # that falls between capture_begin and capture_end would destroy that graph, and free its
+        # tensors, in the middle of this one.  torch.cuda.graph does not collect on entry.  So: collect
+        # now, and keep the collector off until the capture has ended
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         g = torch.cuda.CUDAGraph()
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode=self.capture_error_mode):
-                    self.fn()
+            try:
+                with torch.cuda.stream(s):
+                    with torch.cuda.graph(g, pool=self.pool, stream=s, capture_error_mode=self.capture_error_mode):
+                        self.fn()
+            finally:
+                if gc_was_on:
+                    gc.enable()
             torch.cuda.current_stream().wait_stream(s)
             self.graph = g
             # the capture itself did not execute the step: replay it once now
