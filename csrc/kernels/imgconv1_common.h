@@ -1,7 +1,7 @@
 #pragma once
 // MNIST conv1's padded plane P and its column-shifted copies (see imgconv1_copies.hip): the layout
 // constants and the staging helpers shared by the conv1 kernels and the fused conv1 + conv2 forward
-// (imgconv12_fused.hip).
+// (imgconv12_fused.hip, whose producer waves build the same P and copies row by row).
 #include "common.h"
 
 #include <type_traits>
@@ -77,36 +77,6 @@ __device__ __forceinline__ void build_copies(const bf16* P, bf16* C) {
     static_for_c1<0, HALF>(emit);
   } else {
     static_for_c1<HALF, S>(emit);
-  }
-}
-
-// The 8 forward copies by the first 8 waves of a larger workgroup (the fused forward's 13 waves):
-// wave pair q = threadIdx.x / 128 < 4 takes copies 2q and 2q + 1 - the same windows as
-// build_copies<8>, half as many per thread; threads from 512 on do nothing.
-__device__ __forceinline__ void build_copies8_by4(const bf16* P, bf16* C) {
-  if (threadIdx.x >= 512) return;
-  const int t = threadIdx.x & 127, r = t >> 2, c8 = (t & 3) * 8;
-  const u32x4_t* src = reinterpret_cast<const u32x4_t*>(P + r * PWD + c8);
-  uint32_t d[12];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const u32x4_t v = src[j];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) d[4 * j + e] = v[e];
-  }
-  auto emit = [&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    constexpr int e0 = s + 2;
-    u32x4_t o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (e0 & 1) ? shr16(d[(e0 >> 1) + j], d[(e0 >> 1) + j + 1]) : d[(e0 >> 1) + j];
-    *reinterpret_cast<u32x4_t*>(C + s * CSZ + r * CWD + c8) = o;
-  };
-  switch (threadIdx.x >> 7) {  // uniform per wave
-    case 0: static_for_c1<0, 2>(emit); break;
-    case 1: static_for_c1<2, 4>(emit); break;
-    case 2: static_for_c1<4, 6>(emit); break;
-    default: static_for_c1<6, 8>(emit); break;
   }
 }
 
