@@ -963,9 +963,13 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
                   const optional<Tensor>& mean, const optional<Tensor>& inv_std, const optional<Tensor>& idx,
                   const optional<Tensor>& labels_src, const optional<Tensor>& labels_dst, int64_t seed,
                   const optional<Tensor>& counter, const optional<Tensor>& done, at::TensorList zero,
-                  const optional<Tensor>& onehot, bool shuffle) {
+                  const optional<Tensor>& onehot, bool shuffle, int64_t mix, double label_smoothing) {
   const TensorArgs t("augment_rows", src, "src");
-  TORCH_CHECK(H >= 1 && W >= 1 && C >= 1 && H * W * C < (int64_t(1) << 31), "augment_rows: bad image shape");
+  TORCH_CHECK(mix >= dtfe::MIX_NONE && mix <= dtfe::MIX_CUTMIX, "augment_rows: mix is 0 (none), 1 (mixup) or 2 (cutmix)");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "augment_rows: label_smoothing must lie in [0, 1)");
+  const bool soft = mix != dtfe::MIX_NONE || label_smoothing > 0.0;
+  TORCH_CHECK(!soft || (has(onehot) && has(labels_src)),
+              "augment_rows: mix / label_smoothing write soft label rows: they need onehot and labels_src");  TORCH_CHECK(H >= 1 && W >= 1 && C >= 1 && H * W * C < (int64_t(1) << 31), "augment_rows: bad image shape");
   const int64_t D = H * W * C;
   TORCH_CHECK(src.dim() == 2 && src.size(0) >= 1 && src.size(0) < (int64_t(1) << 31) && src.size(1) == D,
               "augment_rows: src must be [n_rows][H*W*C]");
@@ -974,6 +978,7 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
               "augment_rows: 0 <= pad <= 15 and pad < min(H, W)");
   TORCH_CHECK(has(mean) == has(inv_std), "augment_rows: mean and inv_std come together");
   const int64_t B = dst.size(0);
+  TORCH_CHECK(mix == dtfe::MIX_NONE || B >= 2, "augment_rows: mix needs a batch of B >= 2 (dst)");
   dtfe::AugmentArgs a{};
   const dtfe::AnyPtr ps = t.any(src, "src", dtfe::U8_OR_F32, exactly(src.size(0) * D));
   const dtfe::AnyPtr pd = t.any(dst, "dst", dtfe::F32_OR_BF16, exactly(B * D));
@@ -998,6 +1003,13 @@ void augment_rows(const Tensor& src, const Tensor& dst, int64_t H, int64_t W, in
   a.dst = pd.p; a.dst_dtype = pd.code; a.B = (int)B;
   a.H = (int)H; a.W = (int)W; a.C = (int)C; a.pad = (int)pad; a.flip = flip ? 1 : 0;
   a.seed = (uint64_t)seed;
+  a.mix = (int)mix;
+  if (label_smoothing > 0.0) {  // float32 throughout, as ops.smoothing_values: off = E / ncls, on = (1 - E) + off
+    const float e = (float)label_smoothing;
+    a.smooth_off = e / (float)a.ncls;
+    a.smooth_on = (1.f - e) + a.smooth_off;
+  }
+  a.inv_hw = 1.f / (float)(H * W);
   dtfe::launch_augment_rows(a, t.stream());
 }
 
@@ -1570,7 +1582,7 @@ TORCH_LIBRARY(dtfe, m) {
   m.def(
       "augment_rows(Tensor src, Tensor(a!) dst, int H, int W, int C, int pad, bool flip, Tensor? mean, Tensor? inv_std,"
       " Tensor? idx, Tensor? labels_src, Tensor(b!)? labels_dst, int seed, Tensor(c!)? counter, Tensor(d!)? done,"
-      " Tensor(e!)[] zero, Tensor(f!)? onehot=None, bool shuffle=False) -> ()");
+      " Tensor(e!)[] zero, Tensor(f!)? onehot=None, bool shuffle=False, int mix=0, float label_smoothing=0.0) -> ()");
   m.def("uniform_fill(Tensor(a!) out, float lo, float hi, int seed, Tensor(b!)? counter, Tensor(c!)? done,"
         " Tensor? copy_src=None, Tensor(d!)? copy_dst=None) -> ()");
   m.def("cast_(Tensor src, Tensor(a!) dst) -> ()");

@@ -44,7 +44,8 @@ def channel_stats(images_u8):
 @dataclasses.dataclass(frozen=True)
 class Augment:
     """The input transforms ``ops.augment_rows`` applies to a batch: crop of the ``pad``-padded image,
-    horizontal flip, per-channel standardisation (``mean`` / ``inv_std``: float32 numpy [C])."""
+    horizontal flip, per-channel standardisation (``mean`` / ``inv_std``: float32 numpy [C]); ``mix``
+    ("none" / "mixup" / "cutmix") and ``label_smoothing`` are the label side of the same launch."""
     H: int
     W: int
     C: int
@@ -52,6 +53,8 @@ class Augment:
     flip: bool
     mean: np.ndarray
     inv_std: np.ndarray
+    mix: str = "none"
+    label_smoothing: float = 0.0
 
     @classmethod
     def cifar(cls, train_images_u8):
@@ -60,8 +63,8 @@ class Augment:
         return cls(IMG, IMG, CH, 4, True, mean, inv_std)
 
     def eval(self):
-        """The evaluation-time transform: the same statistics, no crop, no flip."""
-        return dataclasses.replace(self, pad=0, flip=False)
+        """The evaluation-time transform: the same statistics, no crop, no flip, unmixed images, hard labels."""
+        return dataclasses.replace(self, pad=0, flip=False, mix="none", label_smoothing=0.0)
 
     def stats_on(self, device):
         """(mean, inv_std) as float32 tensors on ``device``."""

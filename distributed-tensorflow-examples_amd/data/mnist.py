@@ -136,7 +136,8 @@ class DeviceBatcher:
     ``augment`` (a ``data.cifar.Augment``): every batch goes through ONE ``ops.augment_rows`` launch -
     rows from the host epoch indices as without it, crop / flip draws from a device counter the
     batcher owns (seeded with the DataSet's seed, starting at 0), standardised pixels and the labels
-    (one-hot rows included) written by that launch.  ``out``: its destination instead of ``self.x``,
+    (one-hot rows included; mixed / smoothed ones with ``augment.mix`` / ``augment.label_smoothing``, whose
+    draws come from the same counter) written by that launch.  ``out``: its destination instead of ``self.x``,
     e.g. the program's bf16 input buffer, which then needs no further copy.
 
     ``sampling``: "host" (default) takes the rows from the DataSet's host ``EpochBatcher`` and copies
@@ -213,7 +214,8 @@ class DeviceBatcher:
             self.ops.augment_rows(self.images, x, a.H, a.W, a.C, pad=a.pad, flip=a.flip, mean=self.aug_stats[0],
                                   inv_std=self.aug_stats[1], idx=idx, labels_src=self.labels,
                                   labels_dst=self.y_int, seed=self.aug_seed, counter=self.aug_ctr, done=self.aug_done,
-                                  onehot=self.y if self.one_hot else None, shuffle=shuffle)
+                                  onehot=self.y if self.one_hot else None, shuffle=shuffle, mix=a.mix,
+                                  label_smoothing=a.label_smoothing)
             return x, (self.y if self.one_hot else self.y_int)
         if shuffle:
             self.ops.gather_rows(self.images, self.x, None, self.labels, self.y_int, seed=self.aug_seed,

@@ -9,6 +9,7 @@ distributed machinery, and as the fp32 oracle the kernel tests compare to.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import functools
 import math
@@ -30,7 +31,8 @@ __all__ = [
     "gap_fwd", "gap_bwd", "gemm_group", "seq_stage", "wgrad_tallk", "tallk_ws_floats", "maxpool3_fwd", "maxpool3_bwd", "bn_relu_pool3", "pool3_bn_bwd", "imgconv", "imgwgrad", "hash_u32", "hash_uniform",
     "imgconv_shortcut", "dense_head", "WgradReduces", "conv1_wgrad_pooled_f32",
     "head_xent_f32", "gan_disc_head", "gan_head_ws_floats", "epoch_signal", "grad_norm_plan", "grad_sumsq", "scale_",
-    "augment_rows", "augment_draws", "AUG_SALT", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
+    "augment_rows", "augment_draws", "AUG_SALT", "mix_draws", "mix_r24", "smoothing_values", "MIX_LAM_SALT", "MIX_BOX_SALT",
+    "MIX_ROT_SALT", "MIX_MODES", "epoch_permutation", "shuffled_rows", "SHUF_SALT", "lr_schedule_spec", "lr_schedule_value", "lr_schedule_pack",
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
     "ema_swap", "ema_decay_value", "ema_update_ref",
     "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
@@ -178,6 +180,57 @@ def augment_draws(seed, step, B, pad, flip):
     dy = (h // span) % span
     flipped = ((h // (span * span)) & 1).astype(bool) & bool(flip)
     return dy, dx, flipped
+
+
+# csrc/kernels/augment.h: the streams of mixup's / CutMix's lambda, CutMix's box centre and the partner rotation
+MIX_LAM_SALT = 0x4D1C5EEDB1E2D0A7
+MIX_BOX_SALT = 0xB0C5CE27E4A1F00D
+MIX_ROT_SALT = 0x9A27E4F00D5EED13
+MIX_MODES = {"none": 0, "mixup": 1, "cutmix": 2}
+MixDraws = collections.namedtuple("MixDraws", "shift partner k lam box lam_box")
+
+
+def mix_r24(k):
+    """CutMix's box scale for the 24-bit draw k: floor(sqrt((2^24 - k) * 2^24)) = floor(2^24 * sqrt(1 - lam)),
+    an exact integer (math.isqrt; the kernel corrects a double-precision root against r^2 <= v < (r + 1)^2)."""
+    return math.isqrt(((1 << 24) - int(k)) << 24)
+
+
+def mix_draws(seed, step, B, H, W):
+    """Host mirror of augment_rows' mixing draws for the batch at counter value ``step`` (augment.h), i = step * B + b:
+    ``shift`` = 1 + hash_u32(seed ^ MIX_ROT_SALT, step) % (B - 1) and ``partner`` [B] = (b + shift) % B, a rotation
+    without a fixed point; ``k`` [B] = hash_u32(seed ^ MIX_LAM_SALT, i) >> 8 and ``lam`` [B] float32 = k * 2^-24
+    (mixup's weight of slot b; Uniform[0, 1) = Beta(1, 1)); CutMix's ``box`` (y0, y1, x0, x1), int64 [B] each:
+    half-sides rw = (W * mix_r24(k)) >> 24, rh alike, centre cx = hb % W, cy = (hb / W) % H of
+    hb = hash_u32(seed ^ MIX_BOX_SALT, i), clipped to the image; ``lam_box`` [B] float32 =
+    float32(H * W - box area) * float32(1 / float32(H * W)), the label weight of slot b under CutMix."""
+    B, H, W = int(B), int(H), int(W)
+    if B < 2 or H < 1 or W < 1:
+        raise ValueError("mix_draws: needs B >= 2 and H, W >= 1 (got B = %d, %d x %d)" % (B, H, W))
+    m64 = 0xFFFFFFFFFFFFFFFF
+    seed, s = int(seed) & m64, int(step) & m64
+    i = np.uint64((s * B) & m64) + np.arange(B, dtype=np.uint64)
+    shift = 1 + int(hash_u32(seed ^ MIX_ROT_SALT, np.uint64(s))) % (B - 1)
+    partner = (np.arange(B, dtype=np.int64) + shift) % B
+    k = (hash_u32(seed ^ MIX_LAM_SALT, i) >> np.uint32(8)).astype(np.int64)
+    lam = k.astype(np.float32) * np.float32(2.0 ** -24)
+    r24 = np.array([mix_r24(v) for v in k], dtype=np.int64)
+    rw, rh = (W * r24) >> 24, (H * r24) >> 24
+    hb = hash_u32(seed ^ MIX_BOX_SALT, i).astype(np.int64)
+    cx, cy = hb % W, (hb // W) % H
+    x0, x1 = np.maximum(cx - rw // 2, 0), np.minimum(cx + rw // 2, W)
+    y0, y1 = np.maximum(cy - rh // 2, 0), np.minimum(cy + rh // 2, H)
+    inv_hw = np.float32(1.0) / np.float32(H * W)
+    lam_box = (H * W - (x1 - x0) * (y1 - y0)).astype(np.float32) * inv_hw
+    return MixDraws(shift, partner, k, lam, (y0, y1, x0, x1), lam_box)
+
+
+def smoothing_values(label_smoothing, ncls):
+    """(on, off) of a label row under label smoothing E, in float32 as the binding computes them:
+    off = E / ncls, on = (1 - E) + off; E = 0 gives exactly (1, 0)."""
+    e = np.float32(label_smoothing)
+    off = e / np.float32(ncls)
+    return np.float32(1.0) - e + off, off
 
 
 SHUF_SALT = 0x5EED0FE90C45A1D3  # csrc/kernels/common.h: the epoch permutations' key is seed ^ SHUF_SALT
@@ -1240,8 +1293,21 @@ def _augment_check(src, dst, H, W, C, pad, mean, inv_std):
             raise ValueError("augment_rows: mean / inv_std must be contiguous f32 [C = %d] on %s" % (C, dst.device))
 
 
+def _mix_check(mix, label_smoothing, B, labels_src, onehot):
+    """The mixing / smoothing argument checks of torch.ops.dtfe.augment_rows, as ValueError on either device."""
+    if mix not in MIX_MODES:
+        raise ValueError("augment_rows: mix is one of %s, not %r" % (", ".join(MIX_MODES), mix))
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError("augment_rows: label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
+    if (mix != "none" or label_smoothing > 0) and (onehot is None or labels_src is None):
+        raise ValueError("augment_rows: mix / label_smoothing write soft label rows: they need onehot and labels_src")
+    if mix != "none" and B < 2:
+        raise ValueError("augment_rows: mix=%r needs a batch of B >= 2, dst holds %d" % (mix, B))
+
+
 def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, idx=None, labels_src=None,
-                 labels_dst=None, seed=0, counter=None, done=None, zero=(), onehot=None, shuffle=False):
+                 labels_dst=None, seed=0, counter=None, done=None, zero=(), onehot=None, shuffle=False, mix="none",
+                 label_smoothing=0.0):
     """gather_rows for image rows [n_rows][H*W*C] (uint8 scaled by 1/255, or f32) -> dst [B][H][W][C]
     (f32 / bf16) with the input transforms in the same launch.  Sample b at counter value s draws
     (dy, dx, flipped) = augment_draws(seed, s, B, pad, flip)[b] and
@@ -1250,14 +1316,22 @@ def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, 
     (v - mean[c]) * inv_std[c] in fp32 inside it (``mean`` None: v).  Rows, labels, one-hot rows, zero
     ranges and the (seed, counter, done) ticket are gather_rows'; ``idx`` None samples the rows
     hash_u32(seed, s * B + b) % n_rows, or with ``shuffle=True`` shuffled_rows(seed, s, B, n_rows) (the
-    draws do not depend on the mode).  pad = 0, flip off, no statistics: gather_rows bit for bit."""
+    draws do not depend on the mode).  pad = 0, flip off, no statistics: gather_rows bit for bit.
+
+    ``label_smoothing`` E in [0, 1): the rows of ``onehot`` hold (on, off) = smoothing_values(E, ncls) instead
+    of (1, 0).  ``mix`` "mixup" / "cutmix" (B >= 2): with d = mix_draws(seed, s, B, H, W) and A the batch as
+    above, slot b is blended with slot d.partner[b] - mixup: fl(fl(lam * A[b]) + fl((1 - lam) * A[partner]));
+    cutmix: A[partner] inside the slot's box of the output, A[b] outside - and its label row is
+    fl(fl(w * t_b) + fl((1 - w) * t_partner)) with w = d.lam or d.lam_box: every product and sum rounded to
+    float32 on its own.  ``labels_dst`` stays slot b's own label."""
     _augment_check(src, dst, H, W, C, pad, mean, inv_std)
     if shuffle and idx is not None:
         raise ValueError("augment_rows: shuffle=True samples the rows itself, it takes no idx")
+    _mix_check(mix, label_smoothing, dst.shape[0], labels_src, onehot)
     H, W, C, pad = int(H), int(W), int(C), int(pad)
     if dst.is_cuda:
         require().augment_rows(src, dst, H, W, C, pad, bool(flip), mean, inv_std, idx, labels_src, labels_dst, seed,
-                               counter, done, list(zero), onehot, bool(shuffle))
+                               counter, done, list(zero), onehot, bool(shuffle), MIX_MODES[mix], float(label_smoothing))
         return dst
     B = dst.shape[0]
     s = int(counter.reshape(-1)[0].item()) if counter is not None else 0
@@ -1276,12 +1350,31 @@ def augment_rows(src, dst, H, W, C, pad=0, flip=False, mean=None, inv_std=None, 
     xs = torch.where(fl.reshape(B, 1), W - 1 - x, x) + (dx.reshape(B, 1) - pad)
     inside = ((ys >= 0) & (ys < H)).reshape(B, H, 1, 1) & ((xs >= 0) & (xs < W)).reshape(B, 1, W, 1)
     got = img[torch.arange(B).reshape(B, 1, 1), ys.clamp(0, H - 1).reshape(B, H, 1), xs.clamp(0, W - 1).reshape(B, 1, W)]
-    dst.copy_(torch.where(inside, got, torch.zeros((), dtype=got.dtype)).reshape(dst.shape).to(dst.dtype))
+    out = torch.where(inside, got, torch.zeros((), dtype=got.dtype))
+    if mix != "none":  # the partner's transformed image is slot partner[b]'s: nothing new is drawn for it
+        d = mix_draws(seed, s, B, H, W)
+        partner = torch.from_numpy(d.partner)
+        if mix == "mixup":
+            w = torch.from_numpy(d.lam)
+            own, other = out * w.reshape(B, 1, 1, 1), out[partner] * (1.0 - w).reshape(B, 1, 1, 1)
+            out = own + other  # three rounded operations, never addcmul / lerp
+        else:
+            w = torch.from_numpy(d.lam_box)
+            y0, y1, x0, x1 = (torch.from_numpy(v).reshape(B, 1) for v in d.box)
+            yy, xx = torch.arange(H).reshape(1, H), torch.arange(W).reshape(1, W)
+            box = ((yy >= y0) & (yy < y1)).reshape(B, H, 1, 1) & ((xx >= x0) & (xx < x1)).reshape(B, 1, W, 1)
+            out = torch.where(box, out[partner], out)
+    dst.copy_(out.reshape(dst.shape).to(dst.dtype))
     if labels_dst is not None:
         labels_dst.copy_(labels_src[rows])
     if onehot is not None:
-        onehot.zero_()
-        onehot.scatter_(1, labels_src[rows].long().unsqueeze(1), 1.0)
+        on, off = smoothing_values(label_smoothing, onehot.shape[1])
+        t = torch.full(onehot.shape, float(off))
+        t.scatter_(1, labels_src[rows].long().unsqueeze(1), float(on))
+        if mix != "none":
+            own, other = t * w.reshape(B, 1), t[partner] * (1.0 - w).reshape(B, 1)
+            t = own + other
+        onehot.copy_(t)
     for z in zero:
         z.zero_()
     if counter is not None and done is not None:  # the kernel's ticket needs both

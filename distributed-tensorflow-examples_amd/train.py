@@ -16,6 +16,7 @@ plus the north-star modes: ``--sync`` (sync SGD with a chief over the ps) and
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import json
 import os
 import sys
@@ -316,6 +317,15 @@ def check_augment(augment: str, model):
                          "apply to --model resnet20 only, not to %r" % (augment, getattr(model, "name", "")))
 
 
+def check_mix(mix: str, label_smoothing: float, augment: str):
+    """--mix / --label_smoothing are written by the augmenting batch launch: they need --augment cifar."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError("--label_smoothing %g: must lie in [0, 1)" % label_smoothing)
+    if augment == "none" and (mix != "none" or label_smoothing > 0):
+        raise ValueError("--mix / --label_smoothing: the mixed images and soft label rows are written by the "
+                         "augmenting batch launch, add --augment cifar (--model resnet20)")
+
+
 class Feeder:
     """next batch for a program: host next_batch on CPU, HBM gather on GPU.
 
@@ -329,14 +339,16 @@ class Feeder:
     so ``next()`` can be captured into the step graph; on CPU the same batcher runs on host tensors through
     the ops' mirrors.  ``seek(k)`` continues at batch k (device mode)."""
 
-    def __init__(self, data, program, device, augment="none", shuffle="host"):
+    def __init__(self, data, program, device, augment="none", shuffle="host", mix="none", label_smoothing=0.0):
         self.B = program.batch_size
         self.shuffle = shuffle
         self.dev = None
         self.aug = None
+        check_mix(mix, label_smoothing, augment)
         if augment != "none":
             check_augment(augment, program.model)
-            self.aug = cifar.Augment.cifar(data.train.images_u8)
+            self.aug = dataclasses.replace(cifar.Augment.cifar(data.train.images_u8), mix=mix,
+                                           label_smoothing=float(label_smoothing))
             self.stats = program.input_norm = self.aug.stats_on(device)
         if device.type == "cuda" or shuffle == "device":
             self.dev = DeviceBatcher(data.train, device, self.B, one_hot=True, augment=self.aug,
@@ -344,6 +356,8 @@ class Feeder:
                                      sampling=shuffle)
         elif self.aug is not None:
             self.x = torch.empty(self.B, self.aug.H * self.aug.W * self.aug.C)
+            self.y = torch.empty(self.B, data.train.num_classes)
+            self.labels = torch.from_numpy(data.train.labels_int.astype(np.int32))
             self.ctr = torch.zeros(1, dtype=torch.int64)
             self.done = torch.zeros(1, dtype=torch.int32)
         self.data = data
@@ -364,11 +378,10 @@ class Feeder:
             a, train = self.aug, self.data.train
             idx = torch.from_numpy(train.next_batch_indices(self.B).astype(np.int32))
             ops.augment_rows(torch.from_numpy(train.images_u8), self.x, a.H, a.W, a.C, pad=a.pad, flip=a.flip,
-                             mean=self.stats[0], inv_std=self.stats[1], idx=idx, seed=train.seed, counter=self.ctr,
-                             done=self.done)
-            y = torch.zeros(self.B, train.num_classes)
-            y[torch.arange(self.B), torch.from_numpy(train.labels_int[idx.numpy()])] = 1.0
-            return self.x, y
+                             mean=self.stats[0], inv_std=self.stats[1], idx=idx, labels_src=self.labels, seed=train.seed,
+                             counter=self.ctr, done=self.done, onehot=self.y, mix=a.mix,
+                             label_smoothing=a.label_smoothing)
+            return self.x, self.y
         x, y = self.data.train.next_batch(self.B)
         return torch.from_numpy(x), torch.from_numpy(y)
 
@@ -545,7 +558,7 @@ def run_worker_ps(flags, model, server, device, log):
         max_to_keep=flags.max_to_keep, log=log)
     data = read_data_sets(model, "" if flags.synthetic else flags.data_dir, one_hot=True,
                           seed=flags.seed * 1000 + server.task_index + 1, log=log)
-    feeder = Feeder(data, prog, device, augment=flags.augment)
+    feeder = Feeder(data, prog, device, augment=flags.augment, mix=flags.mix, label_smoothing=flags.label_smoothing)
     metrics_log = MetricsLog(flags.metrics_jsonl)
     hb = Heartbeat(server.store, "worker", server.task_index, flags.heartbeat_secs)
     faults = FaultInjector("worker", server.task_index, log=log)
@@ -723,7 +736,8 @@ def run_allreduce(flags, model, device, log, world=1, rank=0, group=None, store=
         prog.attach_data_parallel(ar, opts[0])
     data = read_data_sets(model, "" if flags.synthetic else flags.data_dir, one_hot=True, seed=flags.seed * 1000 + rank + 1,
                           log=log if is_chief else (lambda *_: None))
-    feeder = Feeder(data, prog, device, augment=flags.augment, shuffle="device" if dev_shuffle else "host")
+    feeder = Feeder(data, prog, device, augment=flags.augment, shuffle="device" if dev_shuffle else "host", mix=flags.mix,
+                    label_smoothing=flags.label_smoothing)
     # --shuffle device: rows and crop / flip draws are functions of the batch number, so a restored run
     # (the chief's state, broadcast above) continues the epoch order and the augmentation stream
     feeder.seek(int(gstep.item()) // model.gs_increments)
@@ -958,6 +972,7 @@ def run(model_name: str, argv=None, log=_print):
     except ValueError as e:
         raise SystemExit(str(e))
     check_augment(flags.augment, model)
+    check_mix(flags.mix, flags.label_smoothing, flags.augment)
     torch.manual_seed(flags.seed)
     np.random.seed(flags.seed)
     mode = flagmod.resolve_mode(flags)  # (+ mode-dependent defaults: --heartbeat_secs)

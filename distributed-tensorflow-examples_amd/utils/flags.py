@@ -132,6 +132,16 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                          "none (default): pixels / 255 as they are.  The crop / flip draws are a counter-based "
                          "stream seeded with the worker's data seed; a restart begins its counter at 0 again (with "
                          "--shuffle device: at the restored global step)")
+    ap.add_argument("--mix", choices=["none", "mixup", "cutmix"], default="none",
+                    help="blend every training image with a partner of its batch inside the --augment cifar launch "
+                         "(needs it): mixup = lam * image + (1 - lam) * partner, cutmix = a random box of the partner "
+                         "pasted in, the label rows mixed by lam resp. the kept area; lam ~ Uniform[0, 1) = Beta(1, 1). "
+                         "The partner is the batch rotated by a per-step shift, the draws continue the crop / flip "
+                         "stream's counter.  The logged loss is the soft-target cross-entropy; none (default): off")
+    ap.add_argument("--label_smoothing", type=float, default=0.0,
+                    help="E in [0, 1): the training label rows hold 1 - E + E / classes for the label and E / classes "
+                         "elsewhere, written by the --augment cifar launch (needs it); evaluation keeps hard labels.  "
+                         "0 (default): off")
     ap.add_argument("--shuffle", choices=["host", "device"], default="host",
                     help="where a batch's rows are chosen (local / all-reduce modes): host = the host EpochBatcher's "
                          "indices, copied to the device per step (the default); device = a per-epoch permutation of "
