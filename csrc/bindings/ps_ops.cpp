@@ -3,8 +3,10 @@
 // Replaces TF's RecvTensor path (gan/distributed_gan.py:193 - every sess.run pulls the
 // variables from and pushes the gradients to the ps task over gRPC) for a single node:
 //
-//   * shared page   - POSIX shm created by the ps task, mapped + hipHostRegister'ed by it and
-//                     by every worker: one 128-B request/reply slot per worker (ps_link.h).
+//   * shared page   - POSIX shm created by the ps task and mapped by every worker: one 256-B
+//                     request/reply slot per worker (ps_link.h).  The GPUs do not touch the
+//                     mapping: each process has a pinned copy of the page (hipHostMalloc) for its
+//                     own GPU and a relay thread between the two (ps_relay.h).
 //   * IPC buffers   - the ps allocates, per worker, a gradient mailbox and a parameter reply
 //                     buffer in its GPU's memory (uncached) and exports one hipIpc handle;
 //                     workers map it and move bytes with their own copy kernels over xGMI.
@@ -42,6 +44,7 @@
 #include "../kernels/optim.h"
 #include "../kernels/ps_link.h"
 #include "opt_state.h"
+#include "ps_relay.h"
 
 using at::Tensor;
 
@@ -56,10 +59,13 @@ std::mutex g_mu;
 // ------------------------------------------------------------------ shared page
 struct Shm {
   std::string name;
-  size_t bytes = 0;
-  void* host = nullptr;
+  size_t bytes = 0, nslots = 0;
+  void* host = nullptr;  // the POSIX shm mapping: what the hosts of the ps and the workers share
+  void* pin = nullptr;   // this process's pinned copy, `dev` to its GPU (ps_relay.h)
   void* dev = nullptr;
   bool owner = false;
+  std::thread relay;
+  std::atomic<bool> stop{false};
 };
 std::vector<Shm*> g_shm;
 
@@ -69,9 +75,32 @@ Shm* shm_of(int64_t h) {
   return g_shm[h];
 }
 
+// the relay thread of a page: spins like the service thread (a hop adds to every exchange's latency)
+void relay_run(Shm* s) {
+  std::vector<uint64_t> seen(s->nslots * dtfe::PS_NHOPS, 0);
+  auto pass = [&] {
+    return dtfe::ps_relay_pass(reinterpret_cast<uint64_t*>(s->host), reinterpret_cast<uint64_t*>(s->pin), s->nslots,
+                               s->owner, seen);
+  };
+  int idle = 0;
+  while (!s->stop.load(std::memory_order_acquire)) {
+    if (pass()) {
+      idle = 0;
+    } else if (++idle > 64) {
+      idle = 0;
+      sched_yield();
+    }
+  }
+  pass();  // what the GPU wrote before the page's owner synchronized and closed it
+}
+
 int64_t shm_map(const std::string& name, int64_t bytes, bool create) {
+  constexpr int64_t slot_bytes = dtfe::PS_SLOT_WORDS * 8;
+  TORCH_CHECK(bytes > 0 && bytes % slot_bytes == 0 && bytes / slot_bytes <= dtfe::PS_MAX_WORKERS,
+              "dtfe ps: the shared page holds 1..", dtfe::PS_MAX_WORKERS, " worker slots");
   auto* s = new Shm();
   s->name = name;
+  s->nslots = (size_t)(bytes / slot_bytes);
   s->bytes = (size_t)((bytes + 4095) / 4096 * 4096);
   s->owner = create;
   const int fd = create ? shm_open(name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600) : shm_open(name.c_str(), O_RDWR, 0600);
@@ -81,8 +110,17 @@ int64_t shm_map(const std::string& name, int64_t bytes, bool create) {
   close(fd);
   TORCH_CHECK(s->host != MAP_FAILED, "dtfe ps: mmap failed");
   if (create) std::memset(s->host, 0, s->bytes);
-  hchk(hipHostRegister(s->host, s->bytes, hipHostRegisterMapped | hipHostRegisterPortable), "hipHostRegister");
-  hchk(hipHostGetDevicePointer(&s->dev, s->host, 0), "hipHostGetDevicePointer");
+  hipError_t e = hipHostMalloc(&s->pin, s->bytes, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer(&s->dev, s->pin, 0);
+  if (e != hipSuccess) {  // leave no named page behind
+    if (s->pin) (void)hipHostFree(s->pin);
+    munmap(s->host, s->bytes);
+    if (create) shm_unlink(name.c_str());
+    delete s;
+    hchk(e, "hipHostMalloc (handshake page)");
+  }
+  std::memset(s->pin, 0, s->bytes);
+  s->relay = std::thread(relay_run, s);
   std::lock_guard<std::mutex> lk(g_mu);
   g_shm.push_back(s);
   return (int64_t)g_shm.size() - 1;
@@ -100,7 +138,9 @@ void ps_shm_close(int64_t h) {
     g_shm[h] = nullptr;
   }
   if (!s) return;
-  (void)hipHostUnregister(s->host);
+  s->stop.store(true, std::memory_order_release);
+  if (s->relay.joinable()) s->relay.join();
+  (void)hipHostFree(s->pin);
   munmap(s->host, s->bytes);
   if (s->owner) shm_unlink(s->name.c_str());
   delete s;

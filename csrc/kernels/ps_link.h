@@ -4,8 +4,9 @@
 // ps GPU's memory (uncached, exported with hipIpcGetMemHandle, mapped by the worker); a push
 // is the worker's GPU writing its gradients straight into the mailbox over xGMI (or locally
 // when the worker shares the ps's GPU), a pull is its GPU reading the reply buffer.  The
-// request / reply handshake lives in a small shared-memory page mapped into both processes and
-// registered for device access: the worker's GPU publishes "request s" with a system-scope
+// request / reply handshake lives in a small shared-memory page mapped into both processes; each
+// process's GPU reaches it through a pinned copy of the page that a host relay thread keeps in
+// step with the mapping (bindings/ps_relay.h): the worker's GPU publishes "request s" with a system-scope
 // store once its push has completed, the ps's native service thread polls the page, enqueues the
 // fused apply - which writes the worker's reply buffer and the reply words itself - on its own
 // stream; the worker's GPU waits

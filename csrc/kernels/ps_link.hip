@@ -16,7 +16,7 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 // Hand-off discipline (no release fences; one acquire in ps_wait_kernel): mailboxes and reply buffers are uncached
 // device memory, so a store is in memory once it has completed; every copy kernel drains its
 // stores before it ends (the next kernel of the stream starts after it), and the handshake
-// words are system-scope relaxed stores to the host-mapped page, the sequence number issued
+// words are system-scope relaxed stores to the process's pinned host page, the sequence number issued
 // only after the other words have completed.  A system-scope release fence would instead write
 // back every dirty line of the XCD's L2 - tens of microseconds after an apply or a backward
 // (profiles/r4_ps_1p1w_timeline.txt: ps_reply 41-47 us, ps_request 3-4 us).

@@ -5,7 +5,8 @@ through TF's gRPC RecvTensor path on every ``sess.run`` (gan/distributed_gan.py:
 encoder/distributed_encoder.py:165).  On one MI355X node this module replaces that with:
 
 * ps side (``NativeShardService``): per worker a gradient mailbox and a parameter reply buffer
-  in the ps GPU's HBM (one uncached hipIpc allocation), a shared request/reply page, and a C++
+  in the ps GPU's HBM (one uncached hipIpc allocation), a shared request/reply page (each
+  process's GPU sees it through a pinned copy that a host relay thread keeps in step), and a C++
   progress thread that applies every arriving mailbox with the fused TF1 optimizer kernels;
   the apply writes the updated bf16 working copies (and fp32 variables) straight into that
   worker's reply buffer, and its last workgroup advances the step scalars and publishes the
