@@ -1,0 +1,87 @@
+// torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip).
+//
+// As in torch_ops.cpp, every tensor goes through one TensorArgs (tensor_args.h): device, dtype and the exact
+// extent the kernel reads or writes are checked before a pointer leaves it, so a refused call has written nothing.
+#include <ATen/ATen.h>
+#include <torch/library.h>
+
+#include <cstdint>
+
+#include "../kernels/gru_seq.h"
+#include "tensor_args.h"
+
+using at::Tensor;
+using c10::optional;
+using dtfe::exactly;
+using dtfe::has;
+using dtfe::TensorArgs;
+
+namespace {
+
+// the two kernels (Wg [I+H][2H], bg [2H], Wc [I+H][H], bc [H]) of a cell with the sizes already in `a`
+void gru_weights(const TensorArgs& t, dtfe::GruSeqArgs& a, const Tensor& Wg, const Tensor& Wc) {
+  const int64_t KT = a.I + a.H;
+  a.Wg = t.in<float>(Wg, "Wg", exactly(KT * 2 * a.H));
+  a.Wc = t.in<float>(Wc, "Wc", exactly(KT * a.H));
+}
+
+// whole-sequence GRU forward: false (nothing written) when the shape is outside the kernel's (H = 128, I = 28,
+// B % 16 == 0)
+bool gru_seq_fwd(const Tensor& xh, const Tensor& xrh, const Tensor& Wg, const Tensor& bg, const Tensor& Wc,
+                 const Tensor& bc, const Tensor& g, const Tensor& cand, const Tensor& hT) {
+  const TensorArgs t("gru_seq_fwd", xh, "xh");
+  TORCH_CHECK(xh.dim() == 3 && hT.dim() == 2 && xh.size(2) > hT.size(1) && xh.size(0) >= 1 && hT.size(0) == xh.size(1),
+              "gru_seq_fwd: xh [T][B][I+H] f32, hT [B][H]");
+  dtfe::GruSeqArgs a{};
+  a.T = (int)xh.size(0); a.B = (int)xh.size(1); a.H = (int)hT.size(1); a.I = (int)xh.size(2) - a.H;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = t.out<float>(xh, "xh", exactly(TB * (a.I + a.H)));
+  a.xrh = t.out<float>(xrh, "xrh", exactly(TB * (a.I + a.H)));
+  gru_weights(t, a, Wg, Wc);
+  a.bg = t.in<float>(bg, "bg", exactly(2 * a.H)); a.bc = t.in<float>(bc, "bc", exactly(a.H));
+  a.g = t.out<float>(g, "g", exactly(TB * 2 * a.H)); a.cand = t.out<float>(cand, "cand", exactly(TB * a.H));
+  a.hT = t.out<float>(hT, "hT", exactly((int64_t)a.B * a.H));
+  return dtfe::launch_gru_seq_fwd(a, t.stream());
+}
+
+// whole-sequence GRU BPTT; dh_T is dhT, or dl . W_out^T when dl / wo (the fused head's dlogits) are given
+bool gru_seq_bwd(const Tensor& xh, const Tensor& Wg, const Tensor& Wc, const Tensor& g, const Tensor& cand,
+                 const Tensor& dhT, const Tensor& dgg, const Tensor& dgc, const optional<Tensor>& dl,
+                 const optional<Tensor>& wo) {
+  const TensorArgs t("gru_seq_bwd", cand, "cand");
+  TORCH_CHECK(cand.dim() == 3 && cand.size(0) >= 1 && xh.dim() == 3 && xh.size(2) > cand.size(2),
+              "gru_seq_bwd: cand [T][B][H], xh [T][B][I+H]");
+  dtfe::GruSeqArgs a{};
+  a.T = (int)cand.size(0); a.B = (int)cand.size(1); a.H = (int)cand.size(2); a.I = (int)xh.size(2) - a.H;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = const_cast<float*>(t.in<float>(xh, "xh", exactly(TB * (a.I + a.H))));
+  gru_weights(t, a, Wg, Wc);
+  // the kernel reads the recurrent rows with 16-byte loads
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.Wg) % 16 == 0 && reinterpret_cast<uintptr_t>(a.Wc) % 16 == 0,
+              "gru_seq_bwd: Wg and Wc must be 16-byte aligned");
+  a.g = const_cast<float*>(t.in<float>(g, "g", exactly(TB * 2 * a.H)));
+  a.cand = const_cast<float*>(t.in<float>(cand, "cand", exactly(TB * a.H)));
+  a.dhT = t.in<float>(dhT, "dhT", exactly((int64_t)a.B * a.H));
+  a.dgg = t.out<float>(dgg, "dgg", exactly(TB * 2 * a.H)); a.dgc = t.out<float>(dgc, "dgc", exactly(TB * a.H));
+  if (has(dl)) {
+    TORCH_CHECK(has(wo) && wo->dim() == 2 && wo->size(0) == a.H && dl->dim() == 2 && dl->size(0) == a.B &&
+                    dl->size(1) == wo->size(1), "gru_seq_bwd: dl [B][NC] with W_out [H][NC]");
+    a.dl = t.in<float>(dl, "dl", exactly(dl->numel())); a.wo = t.in<float>(wo, "wo", exactly(wo->numel()));
+    a.nc = (int)wo->size(1);
+  }
+  return dtfe::launch_gru_seq_bwd(a, t.stream());
+}
+
+}  // namespace
+
+TORCH_LIBRARY(dtfe_rnn, m) {
+  m.def("gru_seq_fwd(Tensor(a!) xh, Tensor(b!) xrh, Tensor Wg, Tensor bg, Tensor Wc, Tensor bc, Tensor(c!) g,"
+        " Tensor(d!) cand, Tensor(e!) hT) -> bool");
+  m.def("gru_seq_bwd(Tensor xh, Tensor Wg, Tensor Wc, Tensor g, Tensor cand, Tensor dhT, Tensor(a!) dgg,"
+        " Tensor(b!) dgc, Tensor? dl=None, Tensor? wo=None) -> bool");
+}
+
+TORCH_LIBRARY_IMPL(dtfe_rnn, CUDA, m) {
+  m.impl("gru_seq_fwd", &gru_seq_fwd);
+  m.impl("gru_seq_bwd", &gru_seq_bwd);
+}

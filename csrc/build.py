@@ -40,6 +40,9 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 KERNEL_LIB = os.path.join(OUT_DIR, "libdtfe_kernels.so")
+# extra compiler flags of single kernel sources: the GRU's elementwise stages stay scalar fp32 (no packed
+# v_pk_*_f32 forms), so each product and sum rounds exactly as the step-by-step fp32 path does
+FILE_FLAGS = {"gru_seq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 RT_LIB = os.path.join(OUT_DIR, "_dtfe_rt" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 
@@ -119,7 +122,8 @@ def build_kernels(jobs: int, verbose: bool, ab_rev: str | None = None, ab_files=
             kern_srcs = [dst if os.path.abspath(k) == os.path.abspath(f) else k for k in kern_srcs]
         out_lib = os.path.join(ab_dir, "libdtfe_kernels.so")
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        futs = [ex.submit(_compile, s, kflags, HIPCC, verbose) for s in kern_srcs]
+        futs = [ex.submit(_compile, s, kflags + FILE_FLAGS.get(os.path.basename(s), []), HIPCC, verbose)
+                for s in kern_srcs]
         futs += [ex.submit(_compile, s, bflags + ["-x", "hip"], HIPCC, verbose) for s in bind_srcs]
         objs = [f.result() for f in futs]
     link = [HIPCC, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", out_lib + ".tmp"] + objs + [

@@ -1,0 +1,31 @@
+// Persistent whole-sequence GRU forward / BPTT (TF1 tf.nn.rnn_cell.GRUCell), gru_seq.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace dtfe {
+
+struct GruSeqArgs {
+  int T, B, I, H;
+  // [T][B][I+H]: x_t columns and the h_{-1} columns of step 0 given; the forward writes the h_{t-1} columns
+  // of steps 1..T-1 (backward in: h_{t-1})
+  float* xh;
+  float* xrh;        // [T][B][I+H] forward out: x_t columns copied, then r_t * h_{t-1} (the candidate GEMM's rows)
+  const float* Wg;   // [I+H][2H] gates kernel (rows x then h; columns r then u)
+  const float* bg;   // [2H]
+  const float* Wc;   // [I+H][H] candidate kernel (rows x then r * h)
+  const float* bc;   // [H]
+  float* g;          // [T][B][2H] activated r, u (forward out, backward in)
+  float* cand;       // [T][B][H] tanh candidate (forward out, backward in)
+  float* hT;         // [B][H] last hidden state
+  const float* dhT;  // [B][H] d loss / d h_T (backward in), unless dl is given:
+  // dh_T formed in the kernel as dl . W_out^T - dl [B][nc] (the classifier head's dlogits), W_out [H][nc]
+  const float* dl; const float* wo; int nc;
+  float* dgg;        // [T][B][2H] gate pre-activation grads (backward out)
+  float* dgc;        // [T][B][H] candidate pre-activation grads (backward out)
+};
+
+// false, with nothing launched or written, for a shape outside H = 128, I = 28, B % 16 == 0
+bool launch_gru_seq_fwd(const GruSeqArgs& a, hipStream_t s);
+bool launch_gru_seq_bwd(const GruSeqArgs& a, hipStream_t s);
+
+}  // namespace dtfe

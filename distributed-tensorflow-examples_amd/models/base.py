@@ -115,6 +115,10 @@ def zeros_init(shape, g):
     return torch.zeros(*shape)
 
 
+def ones_init(shape, g):
+    return torch.ones(*shape)
+
+
 def glorot_uniform_init(shape, g):
     fan_in, fan_out = shape[0], shape[-1]
     lim = (6.0 / (fan_in + fan_out)) ** 0.5

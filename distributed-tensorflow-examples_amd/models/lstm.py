@@ -15,6 +15,10 @@ gradient is a single [156 x 512] GEMM reducing over all T*B rows at the end
 recurrence and the whole BPTT recurrence are each ONE persistent kernel
 (csrc/kernels/lstm_seq.hip); the per-step path remains for the
 CPU reference and unsupported shapes (DTFE_LSTM_PERSIST=0 forces it).
+
+``set_cell("gru")`` (``--cell gru``) swaps the cell for tf.nn.rnn_cell.GRUCell(128): variables
+rnn/gru_cell/gates/{kernel [156,256], bias [256] (ones)} and rnn/gru_cell/candidate/{kernel [156,128],
+bias [128] (zeros)} in that order, and the step program GruProgram below (csrc/kernels/gru_seq.hip).
 """
 from __future__ import annotations
 
@@ -24,10 +28,11 @@ import torch
 
 from .. import ops
 from ..optim import OptimizerConfig, VarSpec
-from .base import ModelDef, ScaledScalar, StepProgram, glorot_uniform_init, normal_init, zeros_init
+from .base import ModelDef, ScaledScalar, StepProgram, glorot_uniform_init, normal_init, ones_init, zeros_init
 
 T, I, H, NC = 28, 28, 128, 10
 LR = 0.001
+CELLS = ("lstm", "gru")
 
 
 class LstmModel(ModelDef):
@@ -35,21 +40,40 @@ class LstmModel(ModelDef):
     default_batch = 128
     default_steps = 10000
 
-    def __init__(self, lr: float = LR):
-        self.kname, self.bname = "rnn/basic_lstm_cell/kernel", "rnn/basic_lstm_cell/bias"
-        self.specs = [
-            VarSpec("Variable", (H, NC), normal_init(1.0)),
-            VarSpec("Variable_1", (NC,), normal_init(1.0)),
-            VarSpec(self.kname, (I + H, 4 * H), glorot_uniform_init),
-            VarSpec(self.bname, (4 * H,), zeros_init),
-        ]
-        self.var_order = ["Variable", "Variable_1", self.kname, self.bname, "Variable_2"]
+    def __init__(self, lr: float = LR, cell: str = "lstm"):
+        self.lr = lr
+        self.set_cell(cell)
+
+    def set_cell(self, cell: str):
+        """--cell: ``lstm`` = BasicLSTMCell(128) (the reference), ``gru`` = tf.nn.rnn_cell.GRUCell(128) with its
+        TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros)."""
+        if cell not in CELLS:
+            raise ValueError("--cell=%s: the row-sequence model has %s" % (cell, " / ".join(CELLS)))
+        self.cell = cell
+        head = [VarSpec("Variable", (H, NC), normal_init(1.0)), VarSpec("Variable_1", (NC,), normal_init(1.0))]
+        if cell == "gru":
+            self.gk, self.gb = "rnn/gru_cell/gates/kernel", "rnn/gru_cell/gates/bias"
+            self.ck, self.cb = "rnn/gru_cell/candidate/kernel", "rnn/gru_cell/candidate/bias"
+            self.specs = head + [
+                VarSpec(self.gk, (I + H, 2 * H), glorot_uniform_init),
+                VarSpec(self.gb, (2 * H,), ones_init),
+                VarSpec(self.ck, (I + H, H), glorot_uniform_init),
+                VarSpec(self.cb, (H,), zeros_init),
+            ]
+        else:
+            self.kname, self.bname = "rnn/basic_lstm_cell/kernel", "rnn/basic_lstm_cell/bias"
+            self.specs = head + [
+                VarSpec(self.kname, (I + H, 4 * H), glorot_uniform_init),
+                VarSpec(self.bname, (4 * H,), zeros_init),
+            ]
+        self.var_order = [s.name for s in self.specs] + ["Variable_2"]
         self.gs_name = "Variable_2"
-        self.opt_groups = [(OptimizerConfig(kind="sgd", lr=lr), [s.name for s in self.specs],
+        self.opt_groups = [(OptimizerConfig(kind="sgd", lr=self.lr), [s.name for s in self.specs],
                             ("beta1_power", "beta2_power"))]
 
     def program(self, device, batch_size=None, seed: int = 0):
-        return LstmProgram(self, device, batch_size or self.default_batch, seed)
+        cls = GruProgram if self.cell == "gru" else LstmProgram
+        return cls(self, device, batch_size or self.default_batch, seed)
 
 
 class LstmProgram(StepProgram):
@@ -214,3 +238,95 @@ class LstmProgram(StepProgram):
             self.forward()
             hits += int((self.logits[:m].argmax(1) == self.y[:m].argmax(1)).sum().item())
         return hits / n
+
+
+class GruProgram(StepProgram):
+    """The row-sequence model with tf.nn.rnn_cell.GRUCell(128) (LstmModel.set_cell("gru")).
+
+    A GRU step is two dependent GEMMs - the gates over [x_t, h], then the candidate over [x_t, r * h] - so the
+    step program keeps TWO row buffers, xh and xrh, each the A operand of one kernel gradient.  On the GPU the
+    whole forward and the whole BPTT recurrence are one persistent launch each (csrc/kernels/gru_seq.hip, a
+    workgroup per 16 batch rows); there is no per-step HIP path, so the batch must be a multiple of 16 there.
+    On the CPU the same ops run their step-by-step fp32 paths."""
+
+    def __init__(self, model: LstmModel, device, batch_size: int, seed: int = 0):
+        super().__init__(model, device, batch_size, seed)
+        B = batch_size
+        if self.device.type == "cuda" and B % 16:
+            raise ValueError("--cell=gru on the GPU runs whole 16-row groups: batch size %d is not a multiple "
+                             "of 16" % B)
+        f = dict(device=self.device, dtype=torch.float32)
+        self.xh = torch.zeros(T, B, I + H, **f)    # [x_t, h_{t-1}] rows
+        self.xrh = torch.zeros(T, B, I + H, **f)   # [x_t, r_t * h_{t-1}] rows
+        self.g = torch.empty(T, B, 2 * H, **f)     # r, u
+        self.cand = torch.empty(T, B, H, **f)
+        self.hT = torch.empty(B, H, **f)
+        self.logits = torch.empty(B, NC, **f)
+        self.y = torch.empty(B, NC, **f)
+        self.dlogits = torch.empty(B, NC, **f)
+        self.dgg = torch.empty(T, B, 2 * H, **f)
+        self.dgc = torch.empty(T, B, H, **f)
+        self.loss = torch.zeros(1, **f)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+        m = model
+        self.Wo, self.bo = self.P.view("Variable"), self.P.view("Variable_1")
+        self.Wg, self.bg, self.Wc, self.bc = (self.P.view(n) for n in (m.gk, m.gb, m.ck, m.cb))
+        self.gWo, self.gbo = self.P.gview("Variable"), self.P.gview("Variable_1")
+        self.gWg, self.gbg, self.gWc, self.gbc = (self.P.gview(n) for n in (m.gk, m.gb, m.ck, m.cb))
+        # each kernel gradient's own split-K workspace (two wgrad_tallk launches per step)
+        self.k_splits = 32
+        self.ws_g = self.ws_c = None
+        if self.device.type == "cuda":
+            self.ws_g = torch.empty(ops.tallk_ws_floats(I + H, 2 * H, self.k_splits), **f)
+            self.ws_c = torch.empty(ops.tallk_ws_floats(I + H, H, self.k_splits), **f)
+
+    def load_batch(self, batch):
+        x, y = batch
+        B = self.batch_size
+        # image row t is step t; one launch stages x into xh, zeroes h_{-1}, copies the labels and clears the
+        # step's accumulators.  The forward launch copies the x columns on into xrh.
+        if x.dtype == torch.float32 and y.dtype == torch.float32 and x.numel() == B * T * I and y.numel() == B * NC:
+            ops.seq_stage(x, self.xh, T, I, y, self.y, zero=(self.loss, self.correct))
+            self._acc_cleared = True
+            return
+        self.xh[:, :, :I].copy_(x.reshape(B, T, I).transpose(0, 1))
+        self.xh[0, :, I:].zero_()
+        self.y.copy_(y.reshape(B, NC))
+
+    def forward(self, head=False):
+        """The recurrence, then the classifier head: with ``head`` (compute_grads) forward + backward of the head
+        as one launch where it fits (ops.dense_head; returns whether it ran), else the logits GEMM alone."""
+        B = self.batch_size
+        if not ops.gru_seq_fwd(self.xh, self.xrh, self.Wg, self.bg, self.Wc, self.bc, self.g, self.cand, self.hT):
+            raise RuntimeError("gru_seq_fwd declined the shape (B %d, I %d, H %d): no other GRU path" % (B, I, H))
+        if head and ops.dense_head(self.hT, self.Wo, self.bo, self.y, self.logits, self.loss, self.correct,
+                                   self.gWo, self.gbo, None, 1.0 / B, w_fmajor=True, store=True,
+                                   dl_out=self.dlogits):
+            return True
+        ops.gemm(self.hT, self.Wo, self.logits, M=B, N=NC, K=H, bmode=ops.RMAJ, ldb=NC, bias=self.bo)
+        return False
+
+    def compute_grads(self):
+        B = self.batch_size
+        # every gradient element is stored (not accumulated) by this step's kernels
+        if not getattr(self, "_acc_cleared", False):
+            self.loss.zero_()
+            self.correct.zero_()
+        self._acc_cleared = False
+        if not self.forward(head=True):  # a batch too large for the one-workgroup head
+            ops.softmax_xent(self.logits, labels_oh=self.y, scale=1.0 / B, dlogits=self.dlogits, loss_sum=self.loss,
+                             correct=self.correct)
+            ops.gemm(self.hT, self.dlogits, self.gWo, M=H + 1, N=NC, K=B, amode=ops.RMAJ, lda=H, bmode=ops.RMAJ,
+                     ldb=NC, a_ones_row=H, bias_out=self.gbo)
+        # the BPTT launch forms dh_T = dlogits . W_out^T itself (hT stands in for the unused dhT)
+        if not ops.gru_seq_bwd(self.xh, self.Wg, self.Wc, self.g, self.cand, self.hT, self.dgg, self.dgc,
+                               dl=self.dlogits, wo=self.Wo):
+            raise RuntimeError("gru_seq_bwd declined the shape (B %d, I %d, H %d)" % (B, I, H))
+        # kernel + bias gradients over all T*B rows: gWg = [x | h]^T [dr | du], gWc = [x | r h]^T dc
+        ops.wgrad_tallk(self.xh, I + H, self.dgg, 2 * H, I + H, 2 * H, T * B, self.gWg, bias=self.gbg,
+                        splits=self.k_splits, workspace=self.ws_g)
+        ops.wgrad_tallk(self.xrh, I + H, self.dgc, H, I + H, H, T * B, self.gWc, bias=self.gbc,
+                        splits=self.k_splits, workspace=self.ws_c)
+        return {"loss": ScaledScalar(self.loss, 1.0 / B)}
+
+    evaluate = LstmProgram.evaluate  # program-batch chunks, padded: uses load_batch / forward / logits / y only

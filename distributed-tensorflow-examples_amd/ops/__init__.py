@@ -36,6 +36,7 @@ __all__ = [
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
     "ema_swap", "ema_decay_value", "ema_update_ref",
     "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
+    "gru_seq_fwd", "gru_seq_bwd",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -1592,6 +1593,57 @@ def lstm_cell_bwd(act, c_prev, c, dh, dh2, dc_next, dgates, dc_prev):
     dgates.copy_(torch.cat([dc * tj * si * (1 - si), dc * si * (1 - tj * tj), dc * cp * sf * (1 - sf),
                             d * tc * so * (1 - so)], dim=1))
     dc_prev.copy_(dc * sf)
+
+
+# --------------------------------------------------------------------- GRU
+def gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT) -> bool:
+    """Whole-sequence TF1 GRUCell forward.  xh [T][B][I+H] holds x_t in its first I columns and h_{-1} in the
+    h columns of step 0; written: the h_{t-1} columns of steps 1.., xrh [T][B][I+H] = [x_t | r_t * h_{t-1}],
+    g [T][B][2H] = [r | u], cand [T][B][H], hT [B][H].  GPU: one persistent launch (gru_seq.hip); False, with
+    nothing written, for a shape it does not cover (H != 128, I != 28, B % 16).  CPU: fp32, step by step."""
+    if xh.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT))
+    T, H = xh.shape[0], hT.shape[1]
+    I = xh.shape[2] - H
+    h = xh[0, :, I:].clone()
+    for t in range(T):
+        if t > 0:
+            xh[t, :, I:] = h
+        ru = torch.sigmoid(xh[t] @ Wg + bg)
+        r, u = ru[:, :H], ru[:, H:]
+        xrh[t, :, :I] = xh[t, :, :I]
+        xrh[t, :, I:] = r * h
+        c = torch.tanh(xrh[t] @ Wc + bc)
+        h = u * h + (1 - u) * c
+        g[t] = ru
+        cand[t] = c
+    hT.copy_(h)
+    return True
+
+
+def gru_seq_bwd(xh, Wg, Wc, g, cand, dhT, dgg, dgc, dl=None, wo=None) -> bool:
+    """Whole-sequence GRU BPTT from the forward's xh / g / cand: dgg [T][B][2H] and dgc [T][B][H], the gradients
+    of the gate and candidate pre-activations (the kernel gradients are xh^T dgg and xrh^T dgc).  dh_T is dhT,
+    or dl . wo^T when the head's dlogits dl [B][NC] and W_out wo [H][NC] are given.  GPU: one persistent launch;
+    False as for gru_seq_fwd."""
+    if cand.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_seq_bwd(xh, Wg, Wc, g, cand, dhT, dgg, dgc, dl, wo))
+    T, H = cand.shape[0], cand.shape[2]
+    I = xh.shape[2] - H
+    Wgh, Wch = Wg[I:], Wc[I:]
+    dh = dhT if dl is None else dl @ wo.t()
+    for t in range(T - 1, -1, -1):
+        r, u, c, h = g[t, :, :H], g[t, :, H:], cand[t], xh[t, :, I:]
+        dc = dh * (1 - u) * (1 - c * c)
+        du = dh * (h - c) * u * (1 - u)
+        drh = dc @ Wch.t()
+        dgg[t, :, :H] = drh * h * r * (1 - r)
+        dgg[t, :, H:] = du
+        dgc[t] = dc
+        dh = dh * u + drh * r + dgg[t] @ Wgh.t()
+    return True
 
 
 # ------------------------------------------------------------- batch norm

@@ -971,6 +971,14 @@ def run(model_name: str, argv=None, log=_print):
         model.set_dtype(flags.dtype)  # --dtype: the model's program must implement it (no silent fallback)
     except ValueError as e:
         raise SystemExit(str(e))
+    if model_name == "lstm":
+        model.set_cell(flags.cell)
+        if flags.cell == "gru" and flags.device != "cpu" and torch.cuda.is_available() and flags.batch_size % 16:
+            # refused here with a message (GruProgram refuses it again when it is built: no per-step GRU path)
+            raise SystemExit("--cell=gru on the GPU runs whole 16-row groups: --batch_size=%d is not a multiple of 16"
+                             % flags.batch_size)
+    elif flags.cell != "lstm":
+        raise SystemExit("--cell=%s: only the lstm example has a recurrent cell (model %r)" % (flags.cell, model.name))
     check_augment(flags.augment, model)
     check_mix(flags.mix, flags.label_smoothing, flags.augment)
     torch.manual_seed(flags.seed)

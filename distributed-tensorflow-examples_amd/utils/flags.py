@@ -110,6 +110,9 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                     help="compute dtype: fp32 = exact-fp32 MFMA kernels and fp32 activations (the reference's "
                          "precision), bf16 = bf16 MFMA with fp32 accumulation / masters; auto = the model's default. "
                          "GAN / autoencoder / LSTM / softmax: fp32 only; CNN: bf16 (default) or fp32; ResNets: bf16")
+    ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm",
+                    help="recurrent cell of the LSTM example: lstm = BasicLSTMCell(128) (the reference), gru = "
+                         "tf.nn.rnn_cell.GRUCell(128) on its own persistent kernels (GPU: batch a multiple of 16)")
     ap.add_argument("--comm", choices=["auto", "rccl", "ipc", "pg"], default="auto",
                     help="all-reduce engine on GPUs: auto = faster of RCCL / hipIpc two-shot per bucket size "
                          "(both in-graph); pg = torch.distributed ProcessGroupNCCL (eager)")
