@@ -8,7 +8,7 @@ the batch (on-device copy), forward, backward, the TF1 optimizer(s) and the glob
 captured into one hipGraph, on synthetic MNIST-shaped data with the reference batch sizes
 and hyper-parameters.
 
-    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20] [--clip_norm C] [--cell gru]
+    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20] [--clip_norm C] [--cell gru [--rnn_layers L]]
 """
 from __future__ import annotations
 
@@ -29,11 +29,11 @@ from dtfe.train import MODELS  # noqa: E402
 from dtfe.utils.graphs import MultiStepGraph  # noqa: E402
 
 
-def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0, cell="lstm"):
+def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0, cell="lstm", rnn_layers=1):
     cls, lr = MODELS[name]
     model = cls(lr=lr)
     if name == "lstm":
-        model.set_cell(cell)
+        model.set_cell(cell, rnn_layers)
     dev = torch.device("cuda", 0)
     B = model.default_batch
     prog = model.program(dev, B, seed=0)
@@ -63,6 +63,8 @@ def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0
         out.update(clip_norm=clip_norm, global_norm=[round(float(o.global_norm.item()), 6) for o in opts])
     if name == "lstm" and cell != "lstm":
         out.update(cell=cell)
+    if rnn_layers != 1:
+        out.update(rnn_layers=rnn_layers)
     return out
 
 
@@ -76,12 +78,13 @@ def main():
     ap.add_argument("--clip_norm", type=float, default=0.0,
                     help="clip every optimizer's gradients by global norm inside the captured step (0: off)")
     ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm", help="recurrent cell of the lstm row")
+    ap.add_argument("--rnn_layers", type=int, default=1, help="stacked GRU layers of the lstm row (needs --cell gru)")
     a = ap.parse_args()
     if a.clip_norm < 0:
         ap.error("--clip_norm must be >= 0")
     for m in a.models.split(","):
         print(json.dumps(time_model(m, a.steps, a.warmup, graph=not a.no_graph, steps_per_graph=a.steps_per_graph,
-                                    clip_norm=a.clip_norm, cell=a.cell)), flush=True)
+                                    clip_norm=a.clip_norm, cell=a.cell, rnn_layers=a.rnn_layers)), flush=True)
 
 
 if __name__ == "__main__":

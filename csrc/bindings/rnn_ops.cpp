@@ -1,4 +1,4 @@
-// torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip).
+// torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip), single and stacked.
 //
 // As in torch_ops.cpp, every tensor goes through one TensorArgs (tensor_args.h): device, dtype and the exact
 // extent the kernel reads or writes are checked before a pointer leaves it, so a refused call has written nothing.
@@ -25,10 +25,19 @@ void gru_weights(const TensorArgs& t, dtfe::GruSeqArgs& a, const Tensor& Wg, con
   a.Wc = t.in<float>(Wc, "Wc", exactly(KT * a.H));
 }
 
+// optional second destination of every h_t: h2 [T][B][pitch >= H], h_t in the first H columns of row (t, b)
+void gru_h2(const TensorArgs& t, dtfe::GruSeqArgs& a, const optional<Tensor>& h2, const char* op) {
+  if (!has(h2)) return;
+  TORCH_CHECK(h2->dim() == 3 && h2->size(0) == a.T && h2->size(1) == a.B && h2->size(2) >= a.H, op,
+              ": h2 [T][B][pitch >= H]");
+  a.h2p = (int)h2->size(2);
+  a.h2 = t.out<float>(*h2, "h2", exactly((int64_t)a.T * a.B * a.h2p));
+}
+
 // whole-sequence GRU forward: false (nothing written) when the shape is outside the kernel's (H = 128, I = 28,
 // B % 16 == 0)
 bool gru_seq_fwd(const Tensor& xh, const Tensor& xrh, const Tensor& Wg, const Tensor& bg, const Tensor& Wc,
-                 const Tensor& bc, const Tensor& g, const Tensor& cand, const Tensor& hT) {
+                 const Tensor& bc, const Tensor& g, const Tensor& cand, const Tensor& hT, const optional<Tensor>& h2) {
   const TensorArgs t("gru_seq_fwd", xh, "xh");
   TORCH_CHECK(xh.dim() == 3 && hT.dim() == 2 && xh.size(2) > hT.size(1) && xh.size(0) >= 1 && hT.size(0) == xh.size(1),
               "gru_seq_fwd: xh [T][B][I+H] f32, hT [B][H]");
@@ -41,7 +50,31 @@ bool gru_seq_fwd(const Tensor& xh, const Tensor& xrh, const Tensor& Wg, const Te
   a.bg = t.in<float>(bg, "bg", exactly(2 * a.H)); a.bc = t.in<float>(bc, "bc", exactly(a.H));
   a.g = t.out<float>(g, "g", exactly(TB * 2 * a.H)); a.cand = t.out<float>(cand, "cand", exactly(TB * a.H));
   a.hT = t.out<float>(hT, "hT", exactly((int64_t)a.B * a.H));
+  gru_h2(t, a, h2, "gru_seq_fwd");
   return dtfe::launch_gru_seq_fwd(a, t.stream());
+}
+
+// the forward of a stacked layer over projected inputs xpg [T][B][2H] = x . Wg[:I] + bg, xpc [T][B][H] = x . Wc[:I] + bc:
+// false (nothing written) outside H = 128, I % 4 == 0, B % 16 == 0
+bool gru_proj_fwd(const Tensor& xh, const Tensor& xrh, const Tensor& xpg, const Tensor& xpc, const Tensor& Wg,
+                  const Tensor& Wc, const Tensor& g, const Tensor& cand, const Tensor& hT, const optional<Tensor>& h2) {
+  const TensorArgs t("gru_proj_fwd", xh, "xh");
+  TORCH_CHECK(xh.dim() == 3 && hT.dim() == 2 && xh.size(2) > hT.size(1) && xh.size(0) >= 1 && hT.size(0) == xh.size(1),
+              "gru_proj_fwd: xh [T][B][I+H] f32, hT [B][H]");
+  dtfe::GruSeqArgs a{};
+  a.T = (int)xh.size(0); a.B = (int)xh.size(1); a.H = (int)hT.size(1); a.I = (int)xh.size(2) - a.H;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = t.out<float>(xh, "xh", exactly(TB * (a.I + a.H)));
+  a.xrh = t.out<float>(xrh, "xrh", exactly(TB * (a.I + a.H)));
+  // the x columns go from xh to xrh in 16-byte pieces
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.xh) % 16 == 0 && reinterpret_cast<uintptr_t>(a.xrh) % 16 == 0,
+              "gru_proj_fwd: xh and xrh must be 16-byte aligned");
+  a.xpg = t.in<float>(xpg, "xpg", exactly(TB * 2 * a.H)); a.xpc = t.in<float>(xpc, "xpc", exactly(TB * a.H));
+  gru_weights(t, a, Wg, Wc);
+  a.g = t.out<float>(g, "g", exactly(TB * 2 * a.H)); a.cand = t.out<float>(cand, "cand", exactly(TB * a.H));
+  a.hT = t.out<float>(hT, "hT", exactly((int64_t)a.B * a.H));
+  gru_h2(t, a, h2, "gru_proj_fwd");
+  return dtfe::launch_gru_proj_fwd(a, t.stream());
 }
 
 // whole-sequence GRU BPTT; dh_T is dhT, or dl . W_out^T when dl / wo (the fused head's dlogits) are given
@@ -72,16 +105,52 @@ bool gru_seq_bwd(const Tensor& xh, const Tensor& Wg, const Tensor& Wc, const Ten
   return dtfe::launch_gru_seq_bwd(a, t.stream());
 }
 
+// BPTT of one layer of a stack (any I % 4 == 0): dh_t = carry + dhs[t] with dhs [T][B][H] the gradient arriving at
+// every output h_t (the layer above's dx); the recurrence starts from dhT, or dl . W_out^T, or zeros when neither is given
+bool gru_stack_bwd(const Tensor& xh, const Tensor& Wg, const Tensor& Wc, const Tensor& g, const Tensor& cand,
+                   const Tensor& dgg, const Tensor& dgc, const optional<Tensor>& dhs, const optional<Tensor>& dhT,
+                   const optional<Tensor>& dl, const optional<Tensor>& wo) {
+  const TensorArgs t("gru_stack_bwd", cand, "cand");
+  TORCH_CHECK(cand.dim() == 3 && cand.size(0) >= 1 && xh.dim() == 3 && xh.size(2) > cand.size(2),
+              "gru_stack_bwd: cand [T][B][H], xh [T][B][I+H]");
+  TORCH_CHECK(has(dhs) || has(dhT) || has(dl), "gru_stack_bwd: no gradient given (dhs, dhT or dl / wo)");
+  dtfe::GruSeqArgs a{};
+  a.T = (int)cand.size(0); a.B = (int)cand.size(1); a.H = (int)cand.size(2); a.I = (int)xh.size(2) - a.H;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = const_cast<float*>(t.in<float>(xh, "xh", exactly(TB * (a.I + a.H))));
+  gru_weights(t, a, Wg, Wc);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.Wg) % 16 == 0 && reinterpret_cast<uintptr_t>(a.Wc) % 16 == 0,
+              "gru_stack_bwd: Wg and Wc must be 16-byte aligned");
+  a.g = const_cast<float*>(t.in<float>(g, "g", exactly(TB * 2 * a.H)));
+  a.cand = const_cast<float*>(t.in<float>(cand, "cand", exactly(TB * a.H)));
+  a.dgg = t.out<float>(dgg, "dgg", exactly(TB * 2 * a.H)); a.dgc = t.out<float>(dgc, "dgc", exactly(TB * a.H));
+  a.dhs = t.in<float>(dhs, "dhs", exactly(TB * a.H));
+  a.dhT = t.in<float>(dhT, "dhT", exactly((int64_t)a.B * a.H));
+  if (has(dl)) {
+    TORCH_CHECK(has(wo) && wo->dim() == 2 && wo->size(0) == a.H && dl->dim() == 2 && dl->size(0) == a.B &&
+                    dl->size(1) == wo->size(1), "gru_stack_bwd: dl [B][NC] with W_out [H][NC]");
+    a.dl = t.in<float>(dl, "dl", exactly(dl->numel())); a.wo = t.in<float>(wo, "wo", exactly(wo->numel()));
+    a.nc = (int)wo->size(1);
+  }
+  return dtfe::launch_gru_stack_bwd(a, t.stream());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dtfe_rnn, m) {
   m.def("gru_seq_fwd(Tensor(a!) xh, Tensor(b!) xrh, Tensor Wg, Tensor bg, Tensor Wc, Tensor bc, Tensor(c!) g,"
-        " Tensor(d!) cand, Tensor(e!) hT) -> bool");
+        " Tensor(d!) cand, Tensor(e!) hT, Tensor(f!)? h2=None) -> bool");
   m.def("gru_seq_bwd(Tensor xh, Tensor Wg, Tensor Wc, Tensor g, Tensor cand, Tensor dhT, Tensor(a!) dgg,"
         " Tensor(b!) dgc, Tensor? dl=None, Tensor? wo=None) -> bool");
+  m.def("gru_proj_fwd(Tensor(a!) xh, Tensor(b!) xrh, Tensor xpg, Tensor xpc, Tensor Wg, Tensor Wc, Tensor(c!) g,"
+        " Tensor(d!) cand, Tensor(e!) hT, Tensor(f!)? h2=None) -> bool");
+  m.def("gru_stack_bwd(Tensor xh, Tensor Wg, Tensor Wc, Tensor g, Tensor cand, Tensor(a!) dgg, Tensor(b!) dgc,"
+        " Tensor? dhs=None, Tensor? dhT=None, Tensor? dl=None, Tensor? wo=None) -> bool");
 }
 
 TORCH_LIBRARY_IMPL(dtfe_rnn, CUDA, m) {
   m.impl("gru_seq_fwd", &gru_seq_fwd);
   m.impl("gru_seq_bwd", &gru_seq_bwd);
+  m.impl("gru_proj_fwd", &gru_proj_fwd);
+  m.impl("gru_stack_bwd", &gru_stack_bwd);
 }

@@ -22,10 +22,25 @@ struct GruSeqArgs {
   const float* dl; const float* wo; int nc;
   float* dgg;        // [T][B][2H] gate pre-activation grads (backward out)
   float* dgc;        // [T][B][H] candidate pre-activation grads (backward out)
+  // optional second destination of every h_t (both forward kernels): h2[(t B + b) h2p + u], the x columns of the
+  // xh buffer of a layer stacked on this one (h2p = its I' + H)
+  float* h2; int h2p;
+  // the projected-input forward: x_t . Wg[:I] + bg [T][B][2H] and x_t . Wc[:I] + bc [T][B][H] (bg / bc unused)
+  const float* xpg; const float* xpc;
+  // the stacked backward: optional d loss / d h_t arriving at every step [T][B][H] (the layer above's dx_t)
+  const float* dhs;
 };
 
 // false, with nothing launched or written, for a shape outside H = 128, I = 28, B % 16 == 0
 bool launch_gru_seq_fwd(const GruSeqArgs& a, hipStream_t s);
 bool launch_gru_seq_bwd(const GruSeqArgs& a, hipStream_t s);
+
+// The kernels of a stacked layer: any I % 4 == 0 (I is only the row offset of the recurrent rows and part of the xh
+// pitch), H = 128, B % 16 == 0; false with nothing launched otherwise.
+//   forward over projected inputs: the x part of both GEMMs arrives as xpg / xpc, the recurrence multiplies only
+//   by the recurrent rows; xh, xrh 16-byte aligned (the x columns are copied xh -> xrh in 16-byte pieces).
+//   backward: dh_t = carry + dhs[t]; the recurrence starts from dhT or dl . wo^T when given, else from zeros.
+bool launch_gru_proj_fwd(const GruSeqArgs& a, hipStream_t s);
+bool launch_gru_stack_bwd(const GruSeqArgs& a, hipStream_t s);
 
 }  // namespace dtfe

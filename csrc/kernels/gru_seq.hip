@@ -32,6 +32,11 @@
 //   Step t - 1's saved r, u, c, h are loaded while step t computes.
 //
 // The kernel and bias gradients are two wgrad_tallk launches over (xh, dgg) and (xrh, dgc).
+//
+// Stacked layers (a GRU cell whose input is the h sequence of the cell below) add two kernels on the same ownership:
+// gru_proj_fwd_kernel, a forward whose x part was projected beforehand by throughput GEMMs (described at the kernel),
+// and gru_stack_bwd_kernel, the backward above with the input width as an argument and dh += dhs[t] in phase a.  Both
+// forward kernels can also write every h_t straight into the x columns of the next layer's xh (GruSeqArgs::h2).
 #include "gru_seq.h"
 
 #include "common.h"
@@ -154,17 +159,150 @@ __global__ __launch_bounds__(1024) void gru_seq_fwd_kernel(GruSeqArgs a) {
       As[r * AP + GI + u] = h;
       if (t + 1 < a.T) a.xh[(row_t + B + r) * KT + GI + u] = h;
       else a.hT[(long)(r0 + r) * GH + u] = h;
+      if (a.h2) a.h2[(row_t + r) * a.h2p + u] = h;
     }
     // (the next step's x write touches only the x columns of As, last read in phase A; its barrier orders the rest)
   }
 }
 
-__global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
+// The forward of a layer whose whole input sequence exists before it starts (a stacked layer): the x part of both
+// GEMMs was hoisted into two throughput GEMMs over all T * B rows and arrives as xpg / xpc (biases folded in), so a
+// step is gate GEMM (k = 128) -> sigmoid -> r * h -> candidate GEMM (k = 128 over the two wave halves) and phase A
+// has no x work.  Same ownership as gru_seq_fwd_kernel; the data flow differs:
+//   - only the recurrent rows are register-resident: 32 + 16 = 48 weight VGPRs per lane, whatever I is;
+//   - the accumulators of step t START from this wave's xpg[t] / xpc[t] tile (half 1 of the candidate from zero, so the
+//     projection counts once), each fetched as soon as step t - 1 has consumed its own, two barriers ahead of its use;
+//   - h and r * h are read from LDS as 16-byte vectors: lane group g supplies k = 16 q + 4 g + e of MFMA step (q, e)
+//     (the weights are loaded in the same order), 8 + 4 LDS reads per step instead of 32 + 16;
+//   - the x columns of xrh[t] are copied from xh[t] by the u waves, which have no r * h work in phase A.
+__global__ __launch_bounds__(1024) void gru_proj_fwd_kernel(GruSeqArgs a) {
+  __shared__ __attribute__((aligned(16))) float Hs[LR * DP];  // h_{t-1}
+  __shared__ __attribute__((aligned(16))) float RH[LR * DP];  // r * h_{t-1}
+  __shared__ float Us[LR * RP];                               // u
+  __shared__ float P[2][LR * GH];                             // candidate partials of the two k halves
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r0 = blockIdx.x * LR, B = a.B, I = a.I, kt = I + GH, I4 = I / 4;
+  const int mrow = lane & 15, g = lane >> 4;
+  const int tile = w & 7, half = w >> 3;
+  f32x4_t wg[8], wc[4];
+  {
+    const float* p = a.Wg + (long)(I + 4 * g) * (2 * GH) + 16 * w + mrow;
+    const float* q = a.Wc + (long)(I + 64 * half + 4 * g) * GH + 16 * tile + mrow;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wg[k][e] = p[(long)(16 * k + e) * (2 * GH)];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) wc[k][e] = q[(long)(16 * k + e) * GH];
+  }
+  float hreg[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int p = tid + 1024 * q, r = p / GH, u = p - r * GH;
+    hreg[q] = a.xh[(long)(r0 + r) * kt + I + u];  // h_{-1}
+    Hs[r * DP + u] = hreg[q];
+  }
+  // every address of a step is a workgroup-uniform base (row_t) plus one of these small per-thread offsets.
+  // This wave's accumulator tiles: rows 4 g + e, gate column 16 w + mrow, candidate column 16 tile + mrow
+  const unsigned og = 4 * g * (2 * GH) + 16 * w + mrow, oc = 4 * g * GH + 16 * tile + mrow;
+  f32x4_t gnext, cnext = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    gnext[e] = (a.xpg + (long)r0 * (2 * GH))[og + e * (2 * GH)];
+    if (half == 0) cnext[e] = (a.xpc + (long)r0 * GH)[oc + e * GH];
+  }
+  for (int t = 0; t < a.T; ++t) {
+    const long row_t = (long)t * B + r0;
+    float* const g_t = a.g + row_t * (2 * GH);
+    float* const xrh_t = a.xrh + row_t * kt;
+    const float* const xh_t = a.xh + row_t * kt;
+    f32x4_t acc = gnext;
+    __syncthreads();
+    // ---- phase A: gates
+    {
+      const float* hrow = Hs + mrow * DP + 4 * g;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const f32x4_t av = *reinterpret_cast<const f32x4_t*>(hrow + 16 * k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wg[k][e], acc, 0, 0, 0);
+      }
+      const int col = 16 * w + mrow;  // 0..127 r, 128..255 u
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int r = 4 * g + e;
+        const float v = sigmoidf_(acc[e]);
+        g_t[og + e * (2 * GH)] = v;
+        if (w < 8) {
+          const float rh = v * Hs[r * DP + col];
+          RH[r * DP + col] = rh;
+          xrh_t[(unsigned)(r * kt + I + col)] = rh;
+        } else {
+          Us[r * RP + col - GH] = v;
+        }
+      }
+      if (w >= 8) {  // x_t -> xrh (the candidate's weight gradient reads it there)
+        for (int i = tid - 512; i < LR * I4; i += 512) {
+          const int r = i / I4;
+          const unsigned o = r * kt + 4 * (i - r * I4);
+          *reinterpret_cast<f32x4_t*>(xrh_t + o) = *reinterpret_cast<const f32x4_t*>(xh_t + o);
+        }
+      }
+    }
+    __syncthreads();
+    // ---- phase B: the candidate, this wave's k half (and the next step's gate tile, now that this one's is used)
+    f32x4_t accc = cnext;
+    if (t + 1 < a.T) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) gnext[e] = (a.xpg + (row_t + B) * (2 * GH))[og + e * (2 * GH)];
+    }
+    {
+      const float* rrow = RH + mrow * DP + 64 * half + 4 * g;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const f32x4_t av = *reinterpret_cast<const f32x4_t*>(rrow + 16 * k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) accc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wc[k][e], accc, 0, 0, 0);
+      }
+      float* pp = P[half] + 16 * tile + mrow;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pp[(4 * g + e) * GH] = accc[e];
+    }
+    __syncthreads();
+    // ---- phase C: candidate activation and the state update (and the next step's candidate tile)
+    if (t + 1 < a.T && half == 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) cnext[e] = (a.xpc + (row_t + B) * GH)[oc + e * GH];
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int p = tid + 1024 * q, r = p / GH, u = p - r * GH;
+      const float c = tanhf(P[0][p] + P[1][p]);
+      const float uu = Us[r * RP + u];
+      const float h = uu * hreg[q] + (1.f - uu) * c;
+      hreg[q] = h;
+      (a.cand + row_t * GH)[(unsigned)p] = c;
+      Hs[r * DP + u] = h;
+      if (t + 1 < a.T) (a.xh + (row_t + B) * kt)[(unsigned)(r * kt + I + u)] = h;
+      else (a.hT + (long)r0 * GH)[(unsigned)p] = h;
+      if (a.h2) (a.h2 + row_t * a.h2p)[(unsigned)(r * a.h2p + u)] = h;
+    }
+    // (the next step's first barrier orders these Hs writes before its reads, and its phase A writes of RH / Us
+    // after this step's reads)
+  }
+}
+
+// BPTT of one layer.  STACK false: the single layer's kernel (I = 28 a constant, one dh_T).  STACK true: I an
+// argument (row offset I, xh pitch I + H) and an optional d loss / d h_t arriving at every step.
+template <bool STACK>
+__device__ __forceinline__ void gru_bwd_body(const GruSeqArgs& a) {
   __shared__ __attribute__((aligned(16))) float DG[LR * DGP];  // [dr~ | du~]
   __shared__ __attribute__((aligned(16))) float DC[LR * DP];   // dc~
   __shared__ float P[2][LR * GH];  // GEMM partials of the two k halves: drh (b -> c), then dh_{t-1} (d -> a)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int r0 = blockIdx.x * LR, B = a.B;
+  const int r0 = blockIdx.x * LR, B = a.B, I = STACK ? a.I : GI, kt = I + GH;
   const int mrow = lane & 15, g = lane >> 4;
   const int tile = w & 7, half = w >> 3;
   // transposed recurrent weights of this wave's 16 units and k half: lane group g supplies k = 16 q + 4 g + e of
@@ -172,8 +310,8 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
   f32x4_t kc[4], ku[4], kr[4];
   {
     const int unit = 16 * tile + mrow;
-    const float* pc = a.Wc + (long)(GI + unit) * GH + 64 * half + 4 * g;
-    const float* pg = a.Wg + (long)(GI + unit) * (2 * GH) + 64 * half + 4 * g;
+    const float* pc = a.Wc + (long)(I + unit) * GH + 64 * half + 4 * g;
+    const float* pg = a.Wg + (long)(I + unit) * (2 * GH) + 64 * half + 4 * g;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       kc[q] = *reinterpret_cast<const f32x4_t*>(pc + 16 * q);
@@ -182,6 +320,7 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
     }
   }
   float carry[NQ], sr[NQ], su[NQ], sc[NQ], sh[NQ];  // step t's saved r, u, c, h_{t-1}
+  float sd[NQ];                                      // STACK: step t's incoming dhs
   auto fetch = [&](int t) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -190,13 +329,14 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
       sr[q] = a.g[row * (2 * GH) + u];
       su[q] = a.g[row * (2 * GH) + GH + u];
       sc[q] = a.cand[row * GH + u];
-      sh[q] = a.xh[row * KT + GI + u];
+      sh[q] = a.xh[row * kt + I + u];
+      if (STACK) sd[q] = a.dhs ? a.dhs[row * GH + u] : 0.f;
     }
   };
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int p = tid + 1024 * q;
-    P[0][p] = dh_t_of(a, r0 + p / GH, p % GH);
+    P[0][p] = (!STACK || a.dl || a.dhT) ? dh_t_of(a, r0 + p / GH, p % GH) : 0.f;  // (a lower layer starts from zeros)
     P[1][p] = 0.f;
     carry[q] = 0.f;
   }
@@ -210,7 +350,8 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
     for (int q = 0; q < NQ; ++q) {
       const int p = tid + 1024 * q, r = p / GH, u = p - r * GH;
       const float rr = sr[q], uu = su[q], c = sc[q], h = sh[q];
-      const float dh = carry[q] + P[0][p] + P[1][p];
+      float dh = carry[q] + P[0][p] + P[1][p];
+      if (STACK) dh += sd[q];
       const float dc = dh * (1.f - uu) * (1.f - c * c);
       const float du = dh * (h - c) * uu * (1.f - uu);
       DC[r * DP + u] = dc;
@@ -277,7 +418,14 @@ __global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) {
   }
 }
 
+__global__ __launch_bounds__(1024) void gru_seq_bwd_kernel(GruSeqArgs a) { gru_bwd_body<false>(a); }
+__global__ __launch_bounds__(1024) void gru_stack_bwd_kernel(GruSeqArgs a) { gru_bwd_body<true>(a); }
+
 bool covered(const GruSeqArgs& a) { return a.H == GH && a.I == GI && a.T >= 1 && a.B >= LR && a.B % LR == 0; }
+
+bool covered_stack(const GruSeqArgs& a) {
+  return a.H == GH && a.I >= 4 && a.I % 4 == 0 && a.T >= 1 && a.B >= LR && a.B % LR == 0;
+}
 
 }  // namespace
 
@@ -290,6 +438,18 @@ bool launch_gru_seq_fwd(const GruSeqArgs& a, hipStream_t s) {
 bool launch_gru_seq_bwd(const GruSeqArgs& a, hipStream_t s) {
   if (!covered(a)) return false;
   hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(a.B / LR), dim3(1024), 0, s, a);
+  return true;
+}
+
+bool launch_gru_proj_fwd(const GruSeqArgs& a, hipStream_t s) {
+  if (!covered_stack(a) || !a.xpg || !a.xpc) return false;
+  hipLaunchKernelGGL(gru_proj_fwd_kernel, dim3(a.B / LR), dim3(1024), 0, s, a);
+  return true;
+}
+
+bool launch_gru_stack_bwd(const GruSeqArgs& a, hipStream_t s) {
+  if (!covered_stack(a)) return false;
+  hipLaunchKernelGGL(gru_stack_bwd_kernel, dim3(a.B / LR), dim3(1024), 0, s, a);
   return true;
 }
 

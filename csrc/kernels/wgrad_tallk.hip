@@ -13,6 +13,7 @@
 // (no LDS), and the next 8 k-steps' operands are in flight while the current ones multiply.
 // Partial slabs [split][MP][N] are summed in split order by a second kernel (bitwise
 // reproducible, no float atomics), which also stores (not accumulates) the gradient.
+// M + 1 <= 320: up to 5 m-tiles per wave (M = 256, the [x | h] rows of a stacked GRU layer, takes the 5-tile build).
 #include "common.h"
 #include "lstm_seq.h"
 
@@ -123,14 +124,15 @@ void launch_wgrad_tallk(const TallKArgs& in, hipStream_t s) {
   if (a.N % TK_BN || a.M < 1 || a.K < 1 || a.splits < 1 || a.lda < a.M || a.ldb < a.N)
     throw std::runtime_error("wgrad_tallk: needs N % 64 == 0, lda >= M, ldb >= N, K >= 1, splits >= 1");
   const int mtiles = (a.M + 1 + 15) / 16;
-  if (mtiles > 4 * 3) throw std::runtime_error("wgrad_tallk: M + 1 <= 192");
+  if (mtiles > 4 * 5) throw std::runtime_error("wgrad_tallk: M + 1 <= 320");
   a.MP = mtiles * 16;
   a.kchunk = ((a.K + a.splits - 1) / a.splits + 3) / 4 * 4;
   a.splits = (a.K + a.kchunk - 1) / a.kchunk;
   const dim3 grid(a.N / TK_BN, a.splits);
   if (mtiles <= 4) hipLaunchKernelGGL(wgrad_tallk_kernel<1>, grid, dim3(256), 0, s, a);
   else if (mtiles <= 8) hipLaunchKernelGGL(wgrad_tallk_kernel<2>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(wgrad_tallk_kernel<3>, grid, dim3(256), 0, s, a);
+  else if (mtiles <= 12) hipLaunchKernelGGL(wgrad_tallk_kernel<3>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(wgrad_tallk_kernel<5>, grid, dim3(256), 0, s, a);  // M = 256: a stacked GRU layer's [x | h] rows
   const long n = (long)(a.M + (a.bias ? 1 : 0)) * a.N;
   hipLaunchKernelGGL(tallk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }

@@ -19,6 +19,10 @@ CPU reference and unsupported shapes (DTFE_LSTM_PERSIST=0 forces it).
 ``set_cell("gru")`` (``--cell gru``) swaps the cell for tf.nn.rnn_cell.GRUCell(128): variables
 rnn/gru_cell/gates/{kernel [156,256], bias [256] (ones)} and rnn/gru_cell/candidate/{kernel [156,128],
 bias [128] (zeros)} in that order, and the step program GruProgram below (csrc/kernels/gru_seq.hip).
+
+``set_cell("gru", layers=L)`` (``--rnn_layers L``, 2..4) stacks L GRU cells, TF1's
+MultiRNNCell([GRUCell(128)] * L): the four variables of every cell under rnn/multi_rnn_cell/cell_<l>/gru_cell/, the
+kernels of cell_0 with 156 rows and of the cells above with 256, and the step program GruStackProgram.
 """
 from __future__ import annotations
 
@@ -33,6 +37,7 @@ from .base import ModelDef, ScaledScalar, StepProgram, glorot_uniform_init, norm
 T, I, H, NC = 28, 28, 128, 10
 LR = 0.001
 CELLS = ("lstm", "gru")
+MAX_LAYERS = 4
 
 
 class LstmModel(ModelDef):
@@ -40,18 +45,33 @@ class LstmModel(ModelDef):
     default_batch = 128
     default_steps = 10000
 
-    def __init__(self, lr: float = LR, cell: str = "lstm"):
+    def __init__(self, lr: float = LR, cell: str = "lstm", layers: int = 1):
         self.lr = lr
-        self.set_cell(cell)
+        self.set_cell(cell, layers)
 
-    def set_cell(self, cell: str):
+    def set_cell(self, cell: str, layers: int = 1):
         """--cell: ``lstm`` = BasicLSTMCell(128) (the reference), ``gru`` = tf.nn.rnn_cell.GRUCell(128) with its
-        TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros)."""
+        TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros).
+        --rnn_layers: ``layers`` > 1 (gru only) = MultiRNNCell of that many GRUCell(128), each cell's four variables
+        in TF1's static_rnn creation order; layers == 1 is the single cell, unchanged."""
         if cell not in CELLS:
             raise ValueError("--cell=%s: the row-sequence model has %s" % (cell, " / ".join(CELLS)))
-        self.cell = cell
+        if not 1 <= layers <= MAX_LAYERS:
+            raise ValueError("--rnn_layers=%d: 1 to %d recurrent layers" % (layers, MAX_LAYERS))
+        if layers > 1 and cell != "gru":
+            raise ValueError("--rnn_layers=%d needs --cell=gru: a stacked %s is not implemented (its split "
+                             "kernels exchange h across workgroups; only the GRU kernels stack)" % (layers, cell))
+        self.cell, self.layers = cell, layers
         head = [VarSpec("Variable", (H, NC), normal_init(1.0)), VarSpec("Variable_1", (NC,), normal_init(1.0))]
-        if cell == "gru":
+        if layers > 1:
+            self.cells, self.specs = [], list(head)  # per layer: (gates kernel, gates bias, candidate kernel, bias)
+            for l in range(layers):
+                pre, rows = "rnn/multi_rnn_cell/cell_%d/gru_cell/" % l, (I if l == 0 else H) + H
+                names = tuple(pre + n for n in ("gates/kernel", "gates/bias", "candidate/kernel", "candidate/bias"))
+                self.cells.append(names)
+                self.specs += [VarSpec(names[0], (rows, 2 * H), glorot_uniform_init), VarSpec(names[1], (2 * H,), ones_init),
+                               VarSpec(names[2], (rows, H), glorot_uniform_init), VarSpec(names[3], (H,), zeros_init)]
+        elif cell == "gru":
             self.gk, self.gb = "rnn/gru_cell/gates/kernel", "rnn/gru_cell/gates/bias"
             self.ck, self.cb = "rnn/gru_cell/candidate/kernel", "rnn/gru_cell/candidate/bias"
             self.specs = head + [
@@ -72,7 +92,7 @@ class LstmModel(ModelDef):
                             ("beta1_power", "beta2_power"))]
 
     def program(self, device, batch_size=None, seed: int = 0):
-        cls = GruProgram if self.cell == "gru" else LstmProgram
+        cls = GruStackProgram if self.layers > 1 else GruProgram if self.cell == "gru" else LstmProgram
         return cls(self, device, batch_size or self.default_batch, seed)
 
 
@@ -330,3 +350,112 @@ class GruProgram(StepProgram):
         return {"loss": ScaledScalar(self.loss, 1.0 / B)}
 
     evaluate = LstmProgram.evaluate  # program-batch chunks, padded: uses load_batch / forward / logits / y only
+
+
+class GruStackProgram(StepProgram):
+    """L stacked GRUCell(128) (LstmModel.set_cell("gru", layers=L), L > 1).
+
+    Layer 0 reads the image rows and runs on the single layer's kernel, which also writes every h_t into the x
+    columns of layer 1's xh.  The input sequence of a layer above is complete before the layer starts, so the x part
+    of both its GEMMs is hoisted out of the recurrence: two exact-fp32 GEMMs over all T * B rows project it (biases in
+    their epilogue) and the persistent kernel gru_proj_fwd starts each step's accumulators from the projections.
+    Backward, top layer first: gru_stack_bwd takes a gradient at every step (dhs), which for layer l is layer
+    l + 1's input gradient dx = dgg . Wg[:I]^T + dgc . Wc[:I]^T - two more GEMMs over T * B rows; layer 0's dx is never
+    formed.  Every buffer is per layer and every gradient is stored, so the step captures into one hipGraph."""
+
+    def __init__(self, model: LstmModel, device, batch_size: int, seed: int = 0):
+        super().__init__(model, device, batch_size, seed)
+        B, L = batch_size, model.layers
+        if self.device.type == "cuda" and B % 16:
+            raise ValueError("--cell=gru on the GPU runs whole 16-row groups: batch size %d is not a multiple "
+                             "of 16" % B)
+        f = dict(device=self.device, dtype=torch.float32)
+        self.In = [I] + [H] * (L - 1)                                        # input width of each layer
+        self.xh = [torch.zeros(T, B, i + H, **f) for i in self.In]           # [x_t, h_{t-1}] rows (h_{-1} = 0)
+        self.xrh = [torch.zeros(T, B, i + H, **f) for i in self.In]          # [x_t, r_t * h_{t-1}] rows
+        self.g = [torch.empty(T, B, 2 * H, **f) for _ in range(L)]
+        self.cand = [torch.empty(T, B, H, **f) for _ in range(L)]
+        self.hT = [torch.empty(B, H, **f) for _ in range(L)]
+        self.dgg = [torch.empty(T, B, 2 * H, **f) for _ in range(L)]
+        self.dgc = [torch.empty(T, B, H, **f) for _ in range(L)]
+        # layers 1..: the projected inputs and the input gradient (the dhs of the layer below)
+        self.xpg = [None] + [torch.empty(T, B, 2 * H, **f) for _ in range(L - 1)]
+        self.xpc = [None] + [torch.empty(T, B, H, **f) for _ in range(L - 1)]
+        self.dx = [None] + [torch.empty(T, B, H, **f) for _ in range(L - 1)]
+        self.logits = torch.empty(B, NC, **f)
+        self.y = torch.empty(B, NC, **f)
+        self.dlogits = torch.empty(B, NC, **f)
+        self.loss = torch.zeros(1, **f)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.Wo, self.bo = self.P.view("Variable"), self.P.view("Variable_1")
+        self.gWo, self.gbo = self.P.gview("Variable"), self.P.gview("Variable_1")
+        self.W = [tuple(self.P.view(n) for n in names) for names in model.cells]    # (Wg, bg, Wc, bc) per layer
+        self.gW = [tuple(self.P.gview(n) for n in names) for names in model.cells]
+        self.k_splits = 32
+        self.ws = [(None, None)] * L  # each kernel gradient's own split-K workspace
+        if self.device.type == "cuda":
+            self.ws = [(torch.empty(ops.tallk_ws_floats(i + H, 2 * H, self.k_splits), **f),
+                        torch.empty(ops.tallk_ws_floats(i + H, H, self.k_splits), **f)) for i in self.In]
+
+    def load_batch(self, batch):
+        x, y = batch
+        B = self.batch_size
+        if x.dtype == torch.float32 and y.dtype == torch.float32 and x.numel() == B * T * I and y.numel() == B * NC:
+            ops.seq_stage(x, self.xh[0], T, I, y, self.y, zero=(self.loss, self.correct))
+            self._acc_cleared = True
+            return
+        self.xh[0][:, :, :I].copy_(x.reshape(B, T, I).transpose(0, 1))
+        self.xh[0][0, :, I:].zero_()
+        self.y.copy_(y.reshape(B, NC))
+
+    def forward(self, head=False):
+        """The L recurrences, then the classifier head on the top layer's h_T (as GruProgram.forward)."""
+        B, L, TB = self.batch_size, len(self.In), T * self.batch_size
+        Wg, bg, Wc, bc = self.W[0]
+        if not ops.gru_seq_fwd(self.xh[0], self.xrh[0], Wg, bg, Wc, bc, self.g[0], self.cand[0], self.hT[0],
+                               h2=self.xh[1]):
+            raise RuntimeError("gru_seq_fwd declined the shape (B %d, I %d, H %d): no other GRU path" % (B, I, H))
+        for l in range(1, L):
+            Wg, bg, Wc, bc = self.W[l]
+            # the x rows of both kernels over the whole sequence: xh's x columns (pitch 2H) . W[:H] + bias
+            ops.gemm(self.xh[l], Wg, self.xpg[l], M=TB, N=2 * H, K=H, lda=2 * H, bmode=ops.RMAJ, ldb=2 * H, bias=bg)
+            ops.gemm(self.xh[l], Wc, self.xpc[l], M=TB, N=H, K=H, lda=2 * H, bmode=ops.RMAJ, ldb=H, bias=bc)
+            if not ops.gru_proj_fwd(self.xh[l], self.xrh[l], self.xpg[l], self.xpc[l], Wg, Wc, self.g[l], self.cand[l],
+                                    self.hT[l], h2=self.xh[l + 1] if l + 1 < L else None):
+                raise RuntimeError("gru_proj_fwd declined the shape (B %d, I %d, H %d)" % (B, H, H))
+        hT = self.hT[-1]
+        if head and ops.dense_head(hT, self.Wo, self.bo, self.y, self.logits, self.loss, self.correct,
+                                   self.gWo, self.gbo, None, 1.0 / B, w_fmajor=True, store=True,
+                                   dl_out=self.dlogits):
+            return True
+        ops.gemm(hT, self.Wo, self.logits, M=B, N=NC, K=H, bmode=ops.RMAJ, ldb=NC, bias=self.bo)
+        return False
+
+    def compute_grads(self):
+        B, L, TB = self.batch_size, len(self.In), T * self.batch_size
+        # every gradient element is stored (not accumulated) by this step's kernels
+        if not getattr(self, "_acc_cleared", False):
+            self.loss.zero_()
+            self.correct.zero_()
+        self._acc_cleared = False
+        if not self.forward(head=True):  # a batch too large for the one-workgroup head
+            ops.softmax_xent(self.logits, labels_oh=self.y, scale=1.0 / B, dlogits=self.dlogits, loss_sum=self.loss,
+                             correct=self.correct)
+            ops.gemm(self.hT[-1], self.dlogits, self.gWo, M=H + 1, N=NC, K=B, amode=ops.RMAJ, lda=H, bmode=ops.RMAJ,
+                     ldb=NC, a_ones_row=H, bias_out=self.gbo)
+        for l in range(L - 1, -1, -1):
+            (Wg, _, Wc, _), (gWg, gbg, gWc, gbc), i = self.W[l], self.gW[l], self.In[l]
+            # the top layer starts from dh_T = dlogits . W_out^T (formed in the launch), the others from zeros + dhs
+            top = dict(dl=self.dlogits, wo=self.Wo) if l == L - 1 else dict(dhs=self.dx[l + 1])
+            if not ops.gru_stack_bwd(self.xh[l], Wg, Wc, self.g[l], self.cand[l], self.dgg[l], self.dgc[l], **top):
+                raise RuntimeError("gru_stack_bwd declined the shape (B %d, I %d, H %d)" % (B, i, H))
+            if l > 0:  # dx = dgg . Wg[:I]^T + dgc . Wc[:I]^T: the gradient at every h_t of the layer below
+                ops.gemm(self.dgg[l], Wg, self.dx[l], M=TB, N=i, K=2 * H, bmode=ops.KMAJ, ldb=2 * H)
+                ops.gemm(self.dgc[l], Wc, self.dx[l], M=TB, N=i, K=H, bmode=ops.KMAJ, ldb=H, beta=1.0)
+            ops.wgrad_tallk(self.xh[l], i + H, self.dgg[l], 2 * H, i + H, 2 * H, TB, gWg, bias=gbg,
+                            splits=self.k_splits, workspace=self.ws[l][0])
+            ops.wgrad_tallk(self.xrh[l], i + H, self.dgc[l], H, i + H, H, TB, gWc, bias=gbc,
+                            splits=self.k_splits, workspace=self.ws[l][1])
+        return {"loss": ScaledScalar(self.loss, 1.0 / B)}
+
+    evaluate = LstmProgram.evaluate  # uses load_batch / forward / logits / y only

@@ -36,7 +36,7 @@ __all__ = [
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
     "ema_swap", "ema_decay_value", "ema_update_ref",
     "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
-    "gru_seq_fwd", "gru_seq_bwd",
+    "gru_seq_fwd", "gru_seq_bwd", "gru_proj_fwd", "gru_stack_bwd",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -1596,14 +1596,16 @@ def lstm_cell_bwd(act, c_prev, c, dh, dh2, dc_next, dgates, dc_prev):
 
 
 # --------------------------------------------------------------------- GRU
-def gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT) -> bool:
+def gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT, h2=None) -> bool:
     """Whole-sequence TF1 GRUCell forward.  xh [T][B][I+H] holds x_t in its first I columns and h_{-1} in the
     h columns of step 0; written: the h_{t-1} columns of steps 1.., xrh [T][B][I+H] = [x_t | r_t * h_{t-1}],
     g [T][B][2H] = [r | u], cand [T][B][H], hT [B][H].  GPU: one persistent launch (gru_seq.hip); False, with
-    nothing written, for a shape it does not cover (H != 128, I != 28, B % 16).  CPU: fp32, step by step."""
+    nothing written, for a shape it does not cover (H != 128, I != 28, B % 16).  CPU: fp32, step by step.
+    ``h2`` [T][B][pitch >= H]: a second destination of every h_t (the first H columns of its rows, the rest
+    untouched) - the x columns of the xh buffer of a layer stacked on this one."""
     if xh.is_cuda:
         require()
-        return bool(torch.ops.dtfe_rnn.gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT))
+        return bool(torch.ops.dtfe_rnn.gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT, h2))
     T, H = xh.shape[0], hT.shape[1]
     I = xh.shape[2] - H
     h = xh[0, :, I:].clone()
@@ -1618,6 +1620,38 @@ def gru_seq_fwd(xh, xrh, Wg, bg, Wc, bc, g, cand, hT) -> bool:
         h = u * h + (1 - u) * c
         g[t] = ru
         cand[t] = c
+        if h2 is not None:
+            h2[t, :, :H] = h
+    hT.copy_(h)
+    return True
+
+
+def gru_proj_fwd(xh, xrh, xpg, xpc, Wg, Wc, g, cand, hT, h2=None) -> bool:
+    """gru_seq_fwd for a layer whose whole input sequence exists before it starts (a stacked layer): the x part of
+    both GEMMs arrives projected, xpg [T][B][2H] = x_t . Wg[:I] + bg and xpc [T][B][H] = x_t . Wc[:I] + bc (two
+    GEMMs over all T * B rows), and the recurrence multiplies only by the recurrent rows Wg[I:], Wc[I:].  Buffers as
+    gru_seq_fwd (the x columns of xrh are copied from xh).  GPU: one persistent launch for H = 128, I % 4 == 0,
+    B % 16 == 0, else False with nothing written.  CPU: fp32, step by step."""
+    if xh.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_proj_fwd(xh, xrh, xpg, xpc, Wg, Wc, g, cand, hT, h2))
+    T, H = xh.shape[0], hT.shape[1]
+    I = xh.shape[2] - H
+    Wgh, Wch = Wg[I:], Wc[I:]
+    h = xh[0, :, I:].clone()
+    for t in range(T):
+        if t > 0:
+            xh[t, :, I:] = h
+        ru = torch.sigmoid(xpg[t] + h @ Wgh)
+        r, u = ru[:, :H], ru[:, H:]
+        xrh[t, :, :I] = xh[t, :, :I]
+        xrh[t, :, I:] = r * h
+        c = torch.tanh(xpc[t] + xrh[t, :, I:] @ Wch)
+        h = u * h + (1 - u) * c
+        g[t] = ru
+        cand[t] = c
+        if h2 is not None:
+            h2[t, :, :H] = h
     hT.copy_(h)
     return True
 
@@ -1635,6 +1669,34 @@ def gru_seq_bwd(xh, Wg, Wc, g, cand, dhT, dgg, dgc, dl=None, wo=None) -> bool:
     Wgh, Wch = Wg[I:], Wc[I:]
     dh = dhT if dl is None else dl @ wo.t()
     for t in range(T - 1, -1, -1):
+        r, u, c, h = g[t, :, :H], g[t, :, H:], cand[t], xh[t, :, I:]
+        dc = dh * (1 - u) * (1 - c * c)
+        du = dh * (h - c) * u * (1 - u)
+        drh = dc @ Wch.t()
+        dgg[t, :, :H] = drh * h * r * (1 - r)
+        dgg[t, :, H:] = du
+        dgc[t] = dc
+        dh = dh * u + drh * r + dgg[t] @ Wgh.t()
+    return True
+
+
+def gru_stack_bwd(xh, Wg, Wc, g, cand, dgg, dgc, dhs=None, dhT=None, dl=None, wo=None) -> bool:
+    """gru_seq_bwd for one layer of a stack, any input width: ``dhs`` [T][B][H] is the gradient arriving at every
+    output h_t (the layer above's dx_t), added to the carried dh of step t.  The recurrence starts from dhT, or
+    dl . wo^T, or - a lower layer, with dhs alone - from zeros.  GPU: one persistent launch for H = 128, I % 4 == 0,
+    B % 16 == 0, else False with nothing written."""
+    if dhs is None and dhT is None and dl is None:
+        raise ValueError("gru_stack_bwd: no gradient given (dhs, dhT or dl / wo)")
+    if cand.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_stack_bwd(xh, Wg, Wc, g, cand, dgg, dgc, dhs, dhT, dl, wo))
+    T, H = cand.shape[0], cand.shape[2]
+    I = xh.shape[2] - H
+    Wgh, Wch = Wg[I:], Wc[I:]
+    dh = dl @ wo.t() if dl is not None else dhT if dhT is not None else torch.zeros_like(cand[0])
+    for t in range(T - 1, -1, -1):
+        if dhs is not None:
+            dh = dh + dhs[t]
         r, u, c, h = g[t, :, :H], g[t, :, H:], cand[t], xh[t, :, I:]
         dc = dh * (1 - u) * (1 - c * c)
         du = dh * (h - c) * u * (1 - u)

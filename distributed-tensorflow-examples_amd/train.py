@@ -972,13 +972,19 @@ def run(model_name: str, argv=None, log=_print):
     except ValueError as e:
         raise SystemExit(str(e))
     if model_name == "lstm":
-        model.set_cell(flags.cell)
+        try:
+            model.set_cell(flags.cell, flags.rnn_layers)  # --rnn_layers > 1 needs --cell=gru
+        except ValueError as e:
+            raise SystemExit(str(e))
         if flags.cell == "gru" and flags.device != "cpu" and torch.cuda.is_available() and flags.batch_size % 16:
             # refused here with a message (GruProgram refuses it again when it is built: no per-step GRU path)
             raise SystemExit("--cell=gru on the GPU runs whole 16-row groups: --batch_size=%d is not a multiple of 16"
                              % flags.batch_size)
     elif flags.cell != "lstm":
         raise SystemExit("--cell=%s: only the lstm example has a recurrent cell (model %r)" % (flags.cell, model.name))
+    elif flags.rnn_layers != 1:
+        raise SystemExit("--rnn_layers=%d: only the lstm example has recurrent layers (model %r)"
+                         % (flags.rnn_layers, model.name))
     check_augment(flags.augment, model)
     check_mix(flags.mix, flags.label_smoothing, flags.augment)
     torch.manual_seed(flags.seed)

@@ -113,6 +113,9 @@ def build_parser(model_defaults: dict | None = None, prog=None):
     ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm",
                     help="recurrent cell of the LSTM example: lstm = BasicLSTMCell(128) (the reference), gru = "
                          "tf.nn.rnn_cell.GRUCell(128) on its own persistent kernels (GPU: batch a multiple of 16)")
+    ap.add_argument("--rnn_layers", type=int, default=1,
+                    help="recurrent layers of the LSTM example (1-4): L > 1 stacks L GRUCell(128) like TF1's "
+                         "MultiRNNCell (variables rnn/multi_rnn_cell/cell_<l>/gru_cell/...) and needs --cell gru")
     ap.add_argument("--comm", choices=["auto", "rccl", "ipc", "pg"], default="auto",
                     help="all-reduce engine on GPUs: auto = faster of RCCL / hipIpc two-shot per bucket size "
                          "(both in-graph); pg = torch.distributed ProcessGroupNCCL (eager)")
