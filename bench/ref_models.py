@@ -8,7 +8,7 @@ the batch (on-device copy), forward, backward, the TF1 optimizer(s) and the glob
 captured into one hipGraph, on synthetic MNIST-shaped data with the reference batch sizes
 and hyper-parameters.
 
-    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20] [--clip_norm C] [--cell gru [--rnn_layers L]]
+    python bench/ref_models.py [--models gan,encoder,lstm] [--steps 200] [--warmup 20] [--clip_norm C] [--cell gru [--rnn_layers L | --bidirectional]]
 """
 from __future__ import annotations
 
@@ -29,11 +29,12 @@ from dtfe.train import MODELS  # noqa: E402
 from dtfe.utils.graphs import MultiStepGraph  # noqa: E402
 
 
-def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0, cell="lstm", rnn_layers=1):
+def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0, cell="lstm", rnn_layers=1,
+               bidirectional=False):
     cls, lr = MODELS[name]
     model = cls(lr=lr)
     if name == "lstm":
-        model.set_cell(cell, rnn_layers)
+        model.set_cell(cell, rnn_layers, bidirectional)
     dev = torch.device("cuda", 0)
     B = model.default_batch
     prog = model.program(dev, B, seed=0)
@@ -65,6 +66,8 @@ def time_model(name, steps, warmup, graph=True, steps_per_graph=1, clip_norm=0.0
         out.update(cell=cell)
     if rnn_layers != 1:
         out.update(rnn_layers=rnn_layers)
+    if bidirectional:
+        out.update(bidirectional=True)
     return out
 
 
@@ -79,12 +82,15 @@ def main():
                     help="clip every optimizer's gradients by global norm inside the captured step (0: off)")
     ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm", help="recurrent cell of the lstm row")
     ap.add_argument("--rnn_layers", type=int, default=1, help="stacked GRU layers of the lstm row (needs --cell gru)")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="bidirectional GRU layer of the lstm row (needs --cell gru, one layer)")
     a = ap.parse_args()
     if a.clip_norm < 0:
         ap.error("--clip_norm must be >= 0")
     for m in a.models.split(","):
         print(json.dumps(time_model(m, a.steps, a.warmup, graph=not a.no_graph, steps_per_graph=a.steps_per_graph,
-                                    clip_norm=a.clip_norm, cell=a.cell, rnn_layers=a.rnn_layers)), flush=True)
+                                    clip_norm=a.clip_norm, cell=a.cell, rnn_layers=a.rnn_layers,
+                                    bidirectional=a.bidirectional and m == "lstm")), flush=True)
 
 
 if __name__ == "__main__":

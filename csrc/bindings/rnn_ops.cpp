@@ -1,4 +1,5 @@
-// torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip), single and stacked.
+// torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip), single and stacked,
+// and the bidirectional layer's paired-direction kernels (csrc/kernels/gru_bidir.hip).
 //
 // As in torch_ops.cpp, every tensor goes through one TensorArgs (tensor_args.h): device, dtype and the exact
 // extent the kernel reads or writes are checked before a pointer leaves it, so a refused call has written nothing.
@@ -135,6 +136,70 @@ bool gru_stack_bwd(const Tensor& xh, const Tensor& Wg, const Tensor& Wc, const T
   return dtfe::launch_gru_stack_bwd(a, t.stream());
 }
 
+// the four variables of both directions of a bidirectional layer (separate tensors: fw / bw variables of the model)
+void gru_bidir_weights(const TensorArgs& t, dtfe::GruBidirArgs& a, const Tensor* const (&Wg)[2],
+                       const Tensor* const (&Wc)[2]) {
+  static const char* const gname[2] = {"Wg0", "Wg1"};
+  static const char* const cname[2] = {"Wc0", "Wc1"};
+  const int64_t KT = a.I + a.H;
+  for (int d = 0; d < 2; ++d) {
+    a.Wg[d] = t.in<float>(*Wg[d], gname[d], exactly(KT * 2 * a.H));
+    a.Wc[d] = t.in<float>(*Wc[d], cname[d], exactly(KT * a.H));
+  }
+}
+
+// both directions of a bidirectional GRU layer in one launch (gru_bidir.hip): every buffer [2][T][B][..], feat [B][2H];
+// false (nothing written) outside H = 128, I = 28, B % 16 == 0
+bool gru_bidir_fwd(const Tensor& xh, const Tensor& xrh, const Tensor& Wg0, const Tensor& bg0, const Tensor& Wc0,
+                   const Tensor& bc0, const Tensor& Wg1, const Tensor& bg1, const Tensor& Wc1, const Tensor& bc1,
+                   const Tensor& g, const Tensor& cand, const Tensor& feat) {
+  const TensorArgs t("gru_bidir_fwd", xh, "xh");
+  TORCH_CHECK(xh.dim() == 4 && xh.size(0) == 2 && xh.size(1) >= 1 && feat.dim() == 2 && feat.size(1) % 2 == 0 &&
+                  xh.size(3) > feat.size(1) / 2 && feat.size(0) == xh.size(2),
+              "gru_bidir_fwd: xh [2][T][B][I+H] f32, feat [B][2H]");
+  dtfe::GruBidirArgs a{};
+  a.T = (int)xh.size(1); a.B = (int)xh.size(2); a.H = (int)feat.size(1) / 2; a.I = (int)xh.size(3) - a.H;
+  const int64_t TB2 = 2 * (int64_t)a.T * a.B;
+  a.xh = t.out<float>(xh, "xh", exactly(TB2 * (a.I + a.H)));
+  a.xrh = t.out<float>(xrh, "xrh", exactly(TB2 * (a.I + a.H)));
+  gru_bidir_weights(t, a, {&Wg0, &Wg1}, {&Wc0, &Wc1});
+  a.bg[0] = t.in<float>(bg0, "bg0", exactly(2 * a.H)); a.bc[0] = t.in<float>(bc0, "bc0", exactly(a.H));
+  a.bg[1] = t.in<float>(bg1, "bg1", exactly(2 * a.H)); a.bc[1] = t.in<float>(bc1, "bc1", exactly(a.H));
+  a.g = t.out<float>(g, "g", exactly(TB2 * 2 * a.H)); a.cand = t.out<float>(cand, "cand", exactly(TB2 * a.H));
+  a.feat = t.out<float>(feat, "feat", exactly((int64_t)a.B * 2 * a.H));
+  return dtfe::launch_gru_bidir_fwd(a, t.stream());
+}
+
+// BPTT of both directions in one launch; direction d starts from columns d H .. of dhT [B][2H], or from
+// dl . wo[d H : (d + 1) H]^T when dl [B][NC] / wo [2H][NC] (the fused head's dlogits) are given
+bool gru_bidir_bwd(const Tensor& xh, const Tensor& Wg0, const Tensor& Wc0, const Tensor& Wg1, const Tensor& Wc1,
+                   const Tensor& g, const Tensor& cand, const Tensor& dhT, const Tensor& dgg, const Tensor& dgc,
+                   const optional<Tensor>& dl, const optional<Tensor>& wo) {
+  const TensorArgs t("gru_bidir_bwd", cand, "cand");
+  TORCH_CHECK(cand.dim() == 4 && cand.size(0) == 2 && cand.size(1) >= 1 && xh.dim() == 4 && xh.size(3) > cand.size(3),
+              "gru_bidir_bwd: cand [2][T][B][H], xh [2][T][B][I+H]");
+  dtfe::GruBidirArgs a{};
+  a.T = (int)cand.size(1); a.B = (int)cand.size(2); a.H = (int)cand.size(3); a.I = (int)xh.size(3) - a.H;
+  const int64_t TB2 = 2 * (int64_t)a.T * a.B;
+  a.xh = const_cast<float*>(t.in<float>(xh, "xh", exactly(TB2 * (a.I + a.H))));
+  gru_bidir_weights(t, a, {&Wg0, &Wg1}, {&Wc0, &Wc1});
+  // the kernel reads the recurrent rows with 16-byte loads
+  for (int d = 0; d < 2; ++d)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(a.Wg[d]) % 16 == 0 && reinterpret_cast<uintptr_t>(a.Wc[d]) % 16 == 0,
+                "gru_bidir_bwd: Wg and Wc of both directions must be 16-byte aligned");
+  a.g = const_cast<float*>(t.in<float>(g, "g", exactly(TB2 * 2 * a.H)));
+  a.cand = const_cast<float*>(t.in<float>(cand, "cand", exactly(TB2 * a.H)));
+  a.dhT = t.in<float>(dhT, "dhT", exactly((int64_t)a.B * 2 * a.H));
+  a.dgg = t.out<float>(dgg, "dgg", exactly(TB2 * 2 * a.H)); a.dgc = t.out<float>(dgc, "dgc", exactly(TB2 * a.H));
+  if (has(dl)) {
+    TORCH_CHECK(has(wo) && wo->dim() == 2 && wo->size(0) == 2 * a.H && dl->dim() == 2 && dl->size(0) == a.B &&
+                    dl->size(1) == wo->size(1), "gru_bidir_bwd: dl [B][NC] with W_out [2H][NC]");
+    a.dl = t.in<float>(dl, "dl", exactly(dl->numel())); a.wo = t.in<float>(wo, "wo", exactly(wo->numel()));
+    a.nc = (int)wo->size(1);
+  }
+  return dtfe::launch_gru_bidir_bwd(a, t.stream());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dtfe_rnn, m) {
@@ -146,6 +211,10 @@ TORCH_LIBRARY(dtfe_rnn, m) {
         " Tensor(d!) cand, Tensor(e!) hT, Tensor(f!)? h2=None) -> bool");
   m.def("gru_stack_bwd(Tensor xh, Tensor Wg, Tensor Wc, Tensor g, Tensor cand, Tensor(a!) dgg, Tensor(b!) dgc,"
         " Tensor? dhs=None, Tensor? dhT=None, Tensor? dl=None, Tensor? wo=None) -> bool");
+  m.def("gru_bidir_fwd(Tensor(a!) xh, Tensor(b!) xrh, Tensor Wg0, Tensor bg0, Tensor Wc0, Tensor bc0, Tensor Wg1,"
+        " Tensor bg1, Tensor Wc1, Tensor bc1, Tensor(c!) g, Tensor(d!) cand, Tensor(e!) feat) -> bool");
+  m.def("gru_bidir_bwd(Tensor xh, Tensor Wg0, Tensor Wc0, Tensor Wg1, Tensor Wc1, Tensor g, Tensor cand, Tensor dhT,"
+        " Tensor(a!) dgg, Tensor(b!) dgc, Tensor? dl=None, Tensor? wo=None) -> bool");
 }
 
 TORCH_LIBRARY_IMPL(dtfe_rnn, CUDA, m) {
@@ -153,4 +222,6 @@ TORCH_LIBRARY_IMPL(dtfe_rnn, CUDA, m) {
   m.impl("gru_seq_bwd", &gru_seq_bwd);
   m.impl("gru_proj_fwd", &gru_proj_fwd);
   m.impl("gru_stack_bwd", &gru_stack_bwd);
+  m.impl("gru_bidir_fwd", &gru_bidir_fwd);
+  m.impl("gru_bidir_bwd", &gru_bidir_bwd);
 }

@@ -42,7 +42,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNEL_LIB = os.path.join(OUT_DIR, "libdtfe_kernels.so")
 # extra compiler flags of single kernel sources: the GRU's elementwise stages stay scalar fp32 (no packed
 # v_pk_*_f32 forms), so each product and sum rounds exactly as the step-by-step fp32 path does
-FILE_FLAGS = {"gru_seq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"gru_seq.hip": _NO_PACKED_FP32, "gru_bidir.hip": _NO_PACKED_FP32}
 RT_LIB = os.path.join(OUT_DIR, "_dtfe_rt" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 

@@ -43,4 +43,33 @@ bool launch_gru_seq_bwd(const GruSeqArgs& a, hipStream_t s);
 bool launch_gru_proj_fwd(const GruSeqArgs& a, hipStream_t s);
 bool launch_gru_stack_bwd(const GruSeqArgs& a, hipStream_t s);
 
+// A bidirectional layer, both directions in one launch (gru_bidir.hip).  Every buffer has a leading direction axis:
+// d = 0 runs forward in time, d = 1 backward in time, and row t of direction d belongs to time t.
+struct GruBidirArgs {
+  int T, B, I, H;
+  // [2][T][B][I+H].  xh[0]: as GruSeqArgs::xh.  xh[1]: only the initial state given, in the h columns of step T-1; the
+  // forward reads x_t from xh[0], writes it into the x columns of xh[1][t] and its h into the h columns of step t-1,
+  // so xh[1][t] = [x_t | h_bw(t+1)].  Neither direction writes its initial-state columns.
+  float* xh;
+  float* xrh;           // [2][T][B][I+H] forward out: [x_t | r_t * (the state step t starts from)]
+  const float* Wg[2];   // per direction [I+H][2H]
+  const float* bg[2];   // [2H]
+  const float* Wc[2];   // [I+H][H]
+  const float* bc[2];   // [H]
+  float* g;             // [2][T][B][2H]
+  float* cand;          // [2][T][B][H]
+  float* feat;          // [B][2H] forward out: d = 0's state after time T-1 | d = 1's state after time 0
+  // backward in: d loss / d feat [B][2H], unless dl [B][nc] and wo [2H][nc] are given (direction d starts from
+  // dl . wo[d H : (d + 1) H]^T, formed in the kernel)
+  const float* dhT;
+  const float* dl; const float* wo; int nc;
+  float* dgg;           // [2][T][B][2H] backward out
+  float* dgc;           // [2][T][B][H] backward out
+};
+
+// grid (B / 16, 2); false, with nothing launched or written, outside H = 128, I = 28, T >= 1, B >= 16, B % 16 == 0.
+// The backward reads the recurrent rows of Wg / Wc with 16-byte loads.
+bool launch_gru_bidir_fwd(const GruBidirArgs& a, hipStream_t s);
+bool launch_gru_bidir_bwd(const GruBidirArgs& a, hipStream_t s);
+
 }  // namespace dtfe

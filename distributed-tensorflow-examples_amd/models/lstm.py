@@ -23,6 +23,10 @@ bias [128] (zeros)} in that order, and the step program GruProgram below (csrc/k
 ``set_cell("gru", layers=L)`` (``--rnn_layers L``, 2..4) stacks L GRU cells, TF1's
 MultiRNNCell([GRUCell(128)] * L): the four variables of every cell under rnn/multi_rnn_cell/cell_<l>/gru_cell/, the
 kernels of cell_0 with 156 rows and of the cells above with 256, and the step program GruStackProgram.
+
+``set_cell("gru", bidirectional=True)`` (``--bidirectional``) is TF1's bidirectional_dynamic_rnn(GRUCell(128),
+GRUCell(128), x): the four variables of each cell under bidirectional_rnn/{fw,bw}/gru_cell/, a head over both final
+states (Variable [256, 10]) and the step program GruBidirProgram (csrc/kernels/gru_bidir.hip).
 """
 from __future__ import annotations
 
@@ -45,15 +49,17 @@ class LstmModel(ModelDef):
     default_batch = 128
     default_steps = 10000
 
-    def __init__(self, lr: float = LR, cell: str = "lstm", layers: int = 1):
+    def __init__(self, lr: float = LR, cell: str = "lstm", layers: int = 1, bidirectional: bool = False):
         self.lr = lr
-        self.set_cell(cell, layers)
+        self.set_cell(cell, layers, bidirectional)
 
-    def set_cell(self, cell: str, layers: int = 1):
+    def set_cell(self, cell: str, layers: int = 1, bidirectional: bool = False):
         """--cell: ``lstm`` = BasicLSTMCell(128) (the reference), ``gru`` = tf.nn.rnn_cell.GRUCell(128) with its
         TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros).
         --rnn_layers: ``layers`` > 1 (gru only) = MultiRNNCell of that many GRUCell(128), each cell's four variables
-        in TF1's static_rnn creation order; layers == 1 is the single cell, unchanged."""
+        in TF1's static_rnn creation order; layers == 1 is the single cell, unchanged.
+        --bidirectional (gru, one layer): a forward and a backward GRUCell(128) over the same rows, the head on both
+        final states; the fw cell's variables are created before the bw cell's."""
         if cell not in CELLS:
             raise ValueError("--cell=%s: the row-sequence model has %s" % (cell, " / ".join(CELLS)))
         if not 1 <= layers <= MAX_LAYERS:
@@ -61,9 +67,23 @@ class LstmModel(ModelDef):
         if layers > 1 and cell != "gru":
             raise ValueError("--rnn_layers=%d needs --cell=gru: a stacked %s is not implemented (its split "
                              "kernels exchange h across workgroups; only the GRU kernels stack)" % (layers, cell))
-        self.cell, self.layers = cell, layers
-        head = [VarSpec("Variable", (H, NC), normal_init(1.0)), VarSpec("Variable_1", (NC,), normal_init(1.0))]
-        if layers > 1:
+        if bidirectional and cell != "gru":
+            raise ValueError("--bidirectional needs --cell=gru")
+        if bidirectional and layers != 1:
+            raise ValueError("--bidirectional with --rnn_layers=%d: a stacked bidirectional GRU is not implemented"
+                             % layers)
+        self.cell, self.layers, self.bidirectional = cell, layers, bool(bidirectional)
+        head = [VarSpec("Variable", ((2 * H if bidirectional else H), NC), normal_init(1.0)),
+                VarSpec("Variable_1", (NC,), normal_init(1.0))]
+        if bidirectional:
+            self.cells, self.specs = [], list(head)  # per direction: (gates kernel, gates bias, candidate kernel, bias)
+            for d in ("fw", "bw"):
+                pre = "bidirectional_rnn/%s/gru_cell/" % d
+                names = tuple(pre + n for n in ("gates/kernel", "gates/bias", "candidate/kernel", "candidate/bias"))
+                self.cells.append(names)
+                self.specs += [VarSpec(names[0], (I + H, 2 * H), glorot_uniform_init), VarSpec(names[1], (2 * H,), ones_init),
+                               VarSpec(names[2], (I + H, H), glorot_uniform_init), VarSpec(names[3], (H,), zeros_init)]
+        elif layers > 1:
             self.cells, self.specs = [], list(head)  # per layer: (gates kernel, gates bias, candidate kernel, bias)
             for l in range(layers):
                 pre, rows = "rnn/multi_rnn_cell/cell_%d/gru_cell/" % l, (I if l == 0 else H) + H
@@ -92,7 +112,8 @@ class LstmModel(ModelDef):
                             ("beta1_power", "beta2_power"))]
 
     def program(self, device, batch_size=None, seed: int = 0):
-        cls = GruStackProgram if self.layers > 1 else GruProgram if self.cell == "gru" else LstmProgram
+        cls = (GruBidirProgram if self.bidirectional else GruStackProgram if self.layers > 1
+               else GruProgram if self.cell == "gru" else LstmProgram)
         return cls(self, device, batch_size or self.default_batch, seed)
 
 
@@ -456,6 +477,98 @@ class GruStackProgram(StepProgram):
                             splits=self.k_splits, workspace=self.ws[l][0])
             ops.wgrad_tallk(self.xrh[l], i + H, self.dgc[l], H, i + H, H, TB, gWc, bias=gbc,
                             splits=self.k_splits, workspace=self.ws[l][1])
+        return {"loss": ScaledScalar(self.loss, 1.0 / B)}
+
+    evaluate = LstmProgram.evaluate  # uses load_batch / forward / logits / y only
+
+
+class GruBidirProgram(StepProgram):
+    """A bidirectional GRU layer (LstmModel.set_cell("gru", bidirectional=True)): GRUCell(128) forward in time and
+    GRUCell(128) backward in time over the same image rows, the classifier head on [h_fw(T-1) | h_bw(0)].
+
+    Every recurrence buffer has a leading direction axis (ops.gru_bidir_fwd's contract): the batch is staged once, into
+    xh[0], and the backward-in-time direction copies x_t into its own rows.  On the GPU both directions are ONE
+    persistent launch forward and ONE for the BPTT, grid (B / 16, 2) (csrc/kernels/gru_bidir.hip): the directions are
+    independent, so the second runs on CUs the first leaves idle.  The four kernel gradients read the contiguous
+    slices xh[d] / dgg[d] and xrh[d] / dgc[d]; every gradient is stored, so the step captures into one hipGraph."""
+
+    def __init__(self, model: LstmModel, device, batch_size: int, seed: int = 0):
+        super().__init__(model, device, batch_size, seed)
+        B = batch_size
+        if self.device.type == "cuda" and B % 16:
+            raise ValueError("--cell=gru on the GPU runs whole 16-row groups: batch size %d is not a multiple "
+                             "of 16" % B)
+        f = dict(device=self.device, dtype=torch.float32)
+        self.xh = torch.zeros(2, T, B, I + H, **f)    # [x_t | the state step t starts from]; both initial states 0
+        self.xrh = torch.zeros(2, T, B, I + H, **f)   # [x_t | r_t * state]
+        self.g = torch.empty(2, T, B, 2 * H, **f)
+        self.cand = torch.empty(2, T, B, H, **f)
+        self.feat = torch.empty(B, 2 * H, **f)        # [h_fw after T-1 | h_bw after 0]
+        self.logits = torch.empty(B, NC, **f)
+        self.y = torch.empty(B, NC, **f)
+        self.dlogits = torch.empty(B, NC, **f)
+        self.dgg = torch.empty(2, T, B, 2 * H, **f)
+        self.dgc = torch.empty(2, T, B, H, **f)
+        self.loss = torch.zeros(1, **f)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.Wo, self.bo = self.P.view("Variable"), self.P.view("Variable_1")
+        self.gWo, self.gbo = self.P.gview("Variable"), self.P.gview("Variable_1")
+        self.W = [tuple(self.P.view(n) for n in names) for names in model.cells]    # (Wg, bg, Wc, bc) per direction
+        self.gW = [tuple(self.P.gview(n) for n in names) for names in model.cells]
+        self.k_splits = 32
+        self.ws = [(None, None)] * 2  # each kernel gradient's own split-K workspace
+        if self.device.type == "cuda":
+            self.ws = [(torch.empty(ops.tallk_ws_floats(I + H, 2 * H, self.k_splits), **f),
+                        torch.empty(ops.tallk_ws_floats(I + H, H, self.k_splits), **f)) for _ in range(2)]
+
+    def load_batch(self, batch):
+        x, y = batch
+        B = self.batch_size
+        # staged once, into direction 0's rows (h_{-1} zeroed); xh[1]'s initial state is never written: zeros
+        if x.dtype == torch.float32 and y.dtype == torch.float32 and x.numel() == B * T * I and y.numel() == B * NC:
+            ops.seq_stage(x, self.xh[0], T, I, y, self.y, zero=(self.loss, self.correct))
+            self._acc_cleared = True
+            return
+        self.xh[0, :, :, :I].copy_(x.reshape(B, T, I).transpose(0, 1))
+        self.xh[0, 0, :, I:].zero_()
+        self.y.copy_(y.reshape(B, NC))
+
+    def forward(self, head=False):
+        """Both recurrences in one launch, then the classifier head on feat [B][2H] (as GruProgram.forward)."""
+        B = self.batch_size
+        (Wg0, bg0, Wc0, bc0), (Wg1, bg1, Wc1, bc1) = self.W
+        if not ops.gru_bidir_fwd(self.xh, self.xrh, Wg0, bg0, Wc0, bc0, Wg1, bg1, Wc1, bc1, self.g, self.cand,
+                                 self.feat):
+            raise RuntimeError("gru_bidir_fwd declined the shape (B %d, I %d, H %d): no other GRU path" % (B, I, H))
+        if head and ops.dense_head(self.feat, self.Wo, self.bo, self.y, self.logits, self.loss, self.correct,
+                                   self.gWo, self.gbo, None, 1.0 / B, w_fmajor=True, store=True,
+                                   dl_out=self.dlogits):
+            return True
+        ops.gemm(self.feat, self.Wo, self.logits, M=B, N=NC, K=2 * H, bmode=ops.RMAJ, ldb=NC, bias=self.bo)
+        return False
+
+    def compute_grads(self):
+        B = self.batch_size
+        # every gradient element is stored (not accumulated) by this step's kernels
+        if not getattr(self, "_acc_cleared", False):
+            self.loss.zero_()
+            self.correct.zero_()
+        self._acc_cleared = False
+        if not self.forward(head=True):  # a batch too large for the one-workgroup head
+            ops.softmax_xent(self.logits, labels_oh=self.y, scale=1.0 / B, dlogits=self.dlogits, loss_sum=self.loss,
+                             correct=self.correct)
+            ops.gemm(self.feat, self.dlogits, self.gWo, M=2 * H + 1, N=NC, K=B, amode=ops.RMAJ, lda=2 * H,
+                     bmode=ops.RMAJ, ldb=NC, a_ones_row=2 * H, bias_out=self.gbo)
+        # each direction starts from its half of dlogits . W_out^T, formed in the launch (feat stands in for dhT)
+        if not ops.gru_bidir_bwd(self.xh, self.W[0][0], self.W[0][2], self.W[1][0], self.W[1][2], self.g, self.cand,
+                                 self.feat, self.dgg, self.dgc, dl=self.dlogits, wo=self.Wo):
+            raise RuntimeError("gru_bidir_bwd declined the shape (B %d, I %d, H %d)" % (B, I, H))
+        for d in range(2):  # gWg = [x | state]^T [dr | du], gWc = [x | r state]^T dc, per direction
+            gWg, gbg, gWc, gbc = self.gW[d]
+            ops.wgrad_tallk(self.xh[d], I + H, self.dgg[d], 2 * H, I + H, 2 * H, T * B, gWg, bias=gbg,
+                            splits=self.k_splits, workspace=self.ws[d][0])
+            ops.wgrad_tallk(self.xrh[d], I + H, self.dgc[d], H, I + H, H, T * B, gWc, bias=gbc,
+                            splits=self.k_splits, workspace=self.ws[d][1])
         return {"loss": ScaledScalar(self.loss, 1.0 / B)}
 
     evaluate = LstmProgram.evaluate  # uses load_batch / forward / logits / y only

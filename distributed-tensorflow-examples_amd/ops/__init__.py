@@ -36,7 +36,7 @@ __all__ = [
     "eval_metrics", "eval_state", "eval_state_dict", "eval_rows_ref",
     "ema_swap", "ema_decay_value", "ema_update_ref",
     "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
-    "gru_seq_fwd", "gru_seq_bwd", "gru_proj_fwd", "gru_stack_bwd",
+    "gru_seq_fwd", "gru_seq_bwd", "gru_proj_fwd", "gru_stack_bwd", "gru_bidir_fwd", "gru_bidir_bwd",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -1705,6 +1705,55 @@ def gru_stack_bwd(xh, Wg, Wc, g, cand, dgg, dgc, dhs=None, dhT=None, dl=None, wo
         dgg[t, :, H:] = du
         dgc[t] = dc
         dh = dh * u + drh * r + dgg[t] @ Wgh.t()
+    return True
+
+
+def gru_bidir_fwd(xh, xrh, Wg0, bg0, Wc0, bc0, Wg1, bg1, Wc1, bc1, g, cand, feat) -> bool:
+    """Both directions of a bidirectional GRU layer (TF1 bidirectional_dynamic_rnn of two GRUCells) over one input.
+    Every buffer has a leading direction axis - d = 0 runs forward in time with the weights ``*0``, d = 1 backward in
+    time with ``*1`` - and row t of direction d belongs to time t.
+
+    xh [2][T][B][I+H]: xh[0] as for gru_seq_fwd (x_t in the x columns, h_{-1} in the h columns of step 0; the h
+    columns of steps 1..T-1 are written).  Of xh[1] the caller gives only the initial state, in the h columns of
+    step T-1: x_t is read from xh[0] and written into the x columns of xh[1][t], the state after time t into the h
+    columns of step t - 1, so xh[1][t] = [x_t | h_bw(t+1)].  The initial-state columns of neither direction are
+    written.  xrh [2][T][B][I+H] = [x_t | r_t * state], g [2][T][B][2H], cand [2][T][B][H]; feat [B][2H] = the
+    forward final state (after time T-1) | the backward final state (after time 0).
+
+    GPU: one persistent launch with a grid of (B / 16, 2) (gru_bidir.hip); False, with nothing written, outside
+    H = 128, I = 28, B % 16 == 0.  CPU: gru_seq_fwd's fp32 loop per direction, direction 1 on time-flipped copies."""
+    if xh.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_bidir_fwd(xh, xrh, Wg0, bg0, Wc0, bc0, Wg1, bg1, Wc1, bc1, g, cand, feat))
+    T, H = xh.shape[1], feat.shape[1] // 2
+    I = xh.shape[3] - H
+    gru_seq_fwd(xh[0], xrh[0], Wg0, bg0, Wc0, bc0, g[0], cand[0], feat[:, :H])
+    xh[1, :, :, :I] = xh[0, :, :, :I]
+    # flipping moves the initial state from step T-1 to step 0, where the loop expects it
+    f = [v[1].flip(0) for v in (xh, xrh, g, cand)]
+    gru_seq_fwd(*f[:2], Wg1, bg1, Wc1, bc1, *f[2:], feat[:, H:])
+    xh[1, :T - 1, :, I:] = f[0].flip(0)[:T - 1, :, I:]
+    for dst, src in zip((xrh, g, cand), f[1:]):
+        dst[1] = src.flip(0)
+    return True
+
+
+def gru_bidir_bwd(xh, Wg0, Wc0, Wg1, Wc1, g, cand, dhT, dgg, dgc, dl=None, wo=None) -> bool:
+    """BPTT of both directions of a bidirectional GRU layer from gru_bidir_fwd's xh / g / cand (same buffer contract):
+    dgg [2][T][B][2H] and dgc [2][T][B][H], so that direction d's kernel gradients are xh[d]^T dgg[d] and
+    xrh[d]^T dgc[d].  Direction 0 walks t = T-1..0, direction 1 t = 0..T-1; direction d starts from columns
+    d H .. (d + 1) H - 1 of dhT [B][2H] (d loss / d feat), or from dl . wo[d H : (d + 1) H]^T when the head's dlogits
+    dl [B][NC] and W_out wo [2H][NC] are given.  GPU: one persistent launch, grid (B / 16, 2); False as for
+    gru_bidir_fwd."""
+    if cand.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.gru_bidir_bwd(xh, Wg0, Wc0, Wg1, Wc1, g, cand, dhT, dgg, dgc, dl, wo))
+    H = cand.shape[3]
+    start = lambda d: dict(dl=dl, wo=wo[d * H:(d + 1) * H]) if dl is not None else {}  # noqa: E731
+    gru_seq_bwd(xh[0], Wg0, Wc0, g[0], cand[0], dhT[:, :H], dgg[0], dgc[0], **start(0))
+    og, oc = torch.empty_like(dgg[1]), torch.empty_like(dgc[1])
+    gru_seq_bwd(xh[1].flip(0), Wg1, Wc1, g[1].flip(0), cand[1].flip(0), dhT[:, H:], og, oc, **start(1))
+    dgg[1], dgc[1] = og.flip(0), oc.flip(0)
     return True
 
 

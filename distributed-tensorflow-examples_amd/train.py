@@ -973,7 +973,8 @@ def run(model_name: str, argv=None, log=_print):
         raise SystemExit(str(e))
     if model_name == "lstm":
         try:
-            model.set_cell(flags.cell, flags.rnn_layers)  # --rnn_layers > 1 needs --cell=gru
+            # --rnn_layers > 1 and --bidirectional need --cell=gru
+            model.set_cell(flags.cell, flags.rnn_layers, flags.bidirectional)
         except ValueError as e:
             raise SystemExit(str(e))
         if flags.cell == "gru" and flags.device != "cpu" and torch.cuda.is_available() and flags.batch_size % 16:
@@ -985,6 +986,8 @@ def run(model_name: str, argv=None, log=_print):
     elif flags.rnn_layers != 1:
         raise SystemExit("--rnn_layers=%d: only the lstm example has recurrent layers (model %r)"
                          % (flags.rnn_layers, model.name))
+    elif flags.bidirectional:
+        raise SystemExit("--bidirectional: only the lstm example has a recurrent cell (model %r)" % model.name)
     check_augment(flags.augment, model)
     check_mix(flags.mix, flags.label_smoothing, flags.augment)
     torch.manual_seed(flags.seed)

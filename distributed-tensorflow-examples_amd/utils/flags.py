@@ -116,6 +116,10 @@ def build_parser(model_defaults: dict | None = None, prog=None):
     ap.add_argument("--rnn_layers", type=int, default=1,
                     help="recurrent layers of the LSTM example (1-4): L > 1 stacks L GRUCell(128) like TF1's "
                          "MultiRNNCell (variables rnn/multi_rnn_cell/cell_<l>/gru_cell/...) and needs --cell gru")
+    add_bool(ap, "bidirectional", False,
+             "the LSTM example with --cell gru, one layer: a forward and a backward GRUCell(128) over the same rows like "
+             "TF1's bidirectional_dynamic_rnn (variables bidirectional_rnn/{fw,bw}/gru_cell/...), the head on both "
+             "final states; both directions run as one persistent launch")
     ap.add_argument("--comm", choices=["auto", "rccl", "ipc", "pg"], default="auto",
                     help="all-reduce engine on GPUs: auto = faster of RCCL / hipIpc two-shot per bucket size "
                          "(both in-graph); pg = torch.distributed ProcessGroupNCCL (eager)")
