@@ -80,7 +80,7 @@ def main():
     ap.add_argument("--steps_per_graph", type=int, default=1, help="training steps per hipGraph replay")
     ap.add_argument("--clip_norm", type=float, default=0.0,
                     help="clip every optimizer's gradients by global norm inside the captured step (0: off)")
-    ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm", help="recurrent cell of the lstm row")
+    ap.add_argument("--cell", choices=["lstm", "gru", "lnlstm"], default="lstm", help="recurrent cell of the lstm row")
     ap.add_argument("--rnn_layers", type=int, default=1, help="stacked GRU layers of the lstm row (needs --cell gru)")
     ap.add_argument("--bidirectional", action="store_true",
                     help="bidirectional GRU layer of the lstm row (needs --cell gru, one layer)")

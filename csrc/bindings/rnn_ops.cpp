@@ -1,5 +1,6 @@
 // torch.ops.dtfe_rnn.* bindings: the persistent GRU sequence kernels (csrc/kernels/gru_seq.hip), single and stacked,
-// and the bidirectional layer's paired-direction kernels (csrc/kernels/gru_bidir.hip).
+// the bidirectional layer's paired-direction kernels (csrc/kernels/gru_bidir.hip), and the layer-normalised LSTM
+// sequence kernels (csrc/kernels/lnlstm_seq.hip).
 //
 // As in torch_ops.cpp, every tensor goes through one TensorArgs (tensor_args.h): device, dtype and the exact
 // extent the kernel reads or writes are checked before a pointer leaves it, so a refused call has written nothing.
@@ -9,10 +10,12 @@
 #include <cstdint>
 
 #include "../kernels/gru_seq.h"
+#include "../kernels/lnlstm_seq.h"
 #include "tensor_args.h"
 
 using at::Tensor;
 using c10::optional;
+using dtfe::at_least;
 using dtfe::exactly;
 using dtfe::has;
 using dtfe::TensorArgs;
@@ -200,9 +203,66 @@ bool gru_bidir_bwd(const Tensor& xh, const Tensor& Wg0, const Tensor& Wc0, const
   return dtfe::launch_gru_bidir_bwd(a, t.stream());
 }
 
+// whole-sequence layer-normalised LSTM forward (lnlstm_seq.hip): false (nothing written) outside H = 128, I = 28,
+// B % 16 == 0, B >= 16
+bool lnlstm_seq_fwd(const Tensor& xh, const Tensor& K, const Tensor& ln, const Tensor& zhat, const Tensor& chat,
+                    const Tensor& rs, const Tensor& hT, double forget_bias) {
+  const TensorArgs t("lnlstm_seq_fwd", xh, "xh");
+  TORCH_CHECK(xh.dim() == 3 && hT.dim() == 2 && xh.size(2) > hT.size(1) && xh.size(0) >= 1 && hT.size(0) == xh.size(1),
+              "lnlstm_seq_fwd: xh [T][B][I+H] f32, hT [B][H]");
+  dtfe::LnLstmSeqArgs a{};
+  a.T = (int)xh.size(0); a.B = (int)xh.size(1); a.H = (int)hT.size(1); a.I = (int)xh.size(2) - a.H;
+  a.forget_bias = (float)forget_bias;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.xh = t.out<float>(xh, "xh", exactly(TB * (a.I + a.H)));
+  a.K = t.in<float>(K, "K", exactly((int64_t)(a.I + a.H) * 4 * a.H));
+  a.ln = t.in<float>(ln, "ln", exactly((int64_t)dtfe::LNLSTM_NLN * a.H));
+  a.zhat = t.out<float>(zhat, "zhat", exactly(TB * 4 * a.H));
+  a.chat = t.out<float>(chat, "chat", exactly(TB * a.H));
+  a.rs = t.out<float>(rs, "rs", exactly(TB * dtfe::LNLSTM_NRS));
+  a.hT = t.out<float>(hT, "hT", exactly((int64_t)a.B * a.H));
+  return dtfe::launch_lnlstm_seq_fwd(a, t.stream());
+}
+
+// whole-sequence layer-normalised LSTM BPTT; dh_T is dhT, or dl . W_out^T when dl / wo are given.  ws holds one
+// [10][H] slab of gamma / beta gradients per 16-row workgroup
+bool lnlstm_seq_bwd(const Tensor& K, const Tensor& ln, const Tensor& zhat, const Tensor& chat, const Tensor& rs,
+                    const Tensor& dhT, const Tensor& dg, const Tensor& dln, const Tensor& ws,
+                    const optional<Tensor>& dl, const optional<Tensor>& wo, double forget_bias) {
+  const TensorArgs t("lnlstm_seq_bwd", chat, "chat");
+  TORCH_CHECK(chat.dim() == 3 && chat.size(0) >= 1 && K.dim() == 2 && K.size(0) > chat.size(2),
+              "lnlstm_seq_bwd: chat [T][B][H], K [I+H][4H]");
+  dtfe::LnLstmSeqArgs a{};
+  a.T = (int)chat.size(0); a.B = (int)chat.size(1); a.H = (int)chat.size(2); a.I = (int)K.size(0) - a.H;
+  a.forget_bias = (float)forget_bias;
+  const int64_t TB = (int64_t)a.T * a.B;
+  a.K = t.in<float>(K, "K", exactly((int64_t)(a.I + a.H) * 4 * a.H));
+  // the kernel reads the recurrent rows with 16-byte loads
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.K) % 16 == 0, "lnlstm_seq_bwd: K must be 16-byte aligned");
+  a.ln = t.in<float>(ln, "ln", exactly((int64_t)dtfe::LNLSTM_NLN * a.H));
+  a.zhat = const_cast<float*>(t.in<float>(zhat, "zhat", exactly(TB * 4 * a.H)));
+  a.chat = const_cast<float*>(t.in<float>(chat, "chat", exactly(TB * a.H)));
+  a.rs = const_cast<float*>(t.in<float>(rs, "rs", exactly(TB * dtfe::LNLSTM_NRS)));
+  a.dhT = t.in<float>(dhT, "dhT", exactly((int64_t)a.B * a.H));
+  a.dg = t.out<float>(dg, "dg", exactly(TB * 4 * a.H));
+  a.dln = t.out<float>(dln, "dln", exactly((int64_t)dtfe::LNLSTM_NLN * a.H));
+  a.ws = t.out<float>(ws, "ws", at_least((int64_t)(a.B / 16) * dtfe::LNLSTM_NLN * a.H));
+  if (has(dl)) {
+    TORCH_CHECK(has(wo) && wo->dim() == 2 && wo->size(0) == a.H && dl->dim() == 2 && dl->size(0) == a.B &&
+                    dl->size(1) == wo->size(1), "lnlstm_seq_bwd: dl [B][NC] with W_out [H][NC]");
+    a.dl = t.in<float>(dl, "dl", exactly(dl->numel())); a.wo = t.in<float>(wo, "wo", exactly(wo->numel()));
+    a.nc = (int)wo->size(1);
+  }
+  return dtfe::launch_lnlstm_seq_bwd(a, t.stream());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dtfe_rnn, m) {
+  m.def("lnlstm_seq_fwd(Tensor(a!) xh, Tensor K, Tensor ln, Tensor(b!) zhat, Tensor(c!) chat, Tensor(d!) rs,"
+        " Tensor(e!) hT, float forget_bias=1.0) -> bool");
+  m.def("lnlstm_seq_bwd(Tensor K, Tensor ln, Tensor zhat, Tensor chat, Tensor rs, Tensor dhT, Tensor(a!) dg,"
+        " Tensor(b!) dln, Tensor(c!) ws, Tensor? dl=None, Tensor? wo=None, float forget_bias=1.0) -> bool");
   m.def("gru_seq_fwd(Tensor(a!) xh, Tensor(b!) xrh, Tensor Wg, Tensor bg, Tensor Wc, Tensor bc, Tensor(c!) g,"
         " Tensor(d!) cand, Tensor(e!) hT, Tensor(f!)? h2=None) -> bool");
   m.def("gru_seq_bwd(Tensor xh, Tensor Wg, Tensor Wc, Tensor g, Tensor cand, Tensor dhT, Tensor(a!) dgg,"
@@ -218,6 +278,8 @@ TORCH_LIBRARY(dtfe_rnn, m) {
 }
 
 TORCH_LIBRARY_IMPL(dtfe_rnn, CUDA, m) {
+  m.impl("lnlstm_seq_fwd", &lnlstm_seq_fwd);
+  m.impl("lnlstm_seq_bwd", &lnlstm_seq_bwd);
   m.impl("gru_seq_fwd", &gru_seq_fwd);
   m.impl("gru_seq_bwd", &gru_seq_bwd);
   m.impl("gru_proj_fwd", &gru_proj_fwd);

@@ -20,6 +20,11 @@ CPU reference and unsupported shapes (DTFE_LSTM_PERSIST=0 forces it).
 rnn/gru_cell/gates/{kernel [156,256], bias [256] (ones)} and rnn/gru_cell/candidate/{kernel [156,128],
 bias [128] (zeros)} in that order, and the step program GruProgram below (csrc/kernels/gru_seq.hip).
 
+``set_cell("lnlstm")`` (``--cell lnlstm``) is tf.contrib.rnn.LayerNormBasicLSTMCell(128): variables
+rnn/layer_norm_basic_lstm_cell/kernel [156,512] (no bias), then .../<scope>/gamma [128] (ones) and .../<scope>/beta
+[128] (zeros) for scope = input, transform, forget_gate, output, state, and the step program LnLstmProgram
+(csrc/kernels/lnlstm_seq.hip).  One layer, one direction.
+
 ``set_cell("gru", layers=L)`` (``--rnn_layers L``, 2..4) stacks L GRU cells, TF1's
 MultiRNNCell([GRUCell(128)] * L): the four variables of every cell under rnn/multi_rnn_cell/cell_<l>/gru_cell/, the
 kernels of cell_0 with 156 rows and of the cells above with 256, and the step program GruStackProgram.
@@ -40,8 +45,9 @@ from .base import ModelDef, ScaledScalar, StepProgram, glorot_uniform_init, norm
 
 T, I, H, NC = 28, 28, 128, 10
 LR = 0.001
-CELLS = ("lstm", "gru")
+CELLS = ("lstm", "gru", "lnlstm")
 MAX_LAYERS = 4
+LN_SCOPES = ("input", "transform", "forget_gate", "output", "state")  # LayerNormBasicLSTMCell's creation order
 
 
 class LstmModel(ModelDef):
@@ -55,7 +61,9 @@ class LstmModel(ModelDef):
 
     def set_cell(self, cell: str, layers: int = 1, bidirectional: bool = False):
         """--cell: ``lstm`` = BasicLSTMCell(128) (the reference), ``gru`` = tf.nn.rnn_cell.GRUCell(128) with its
-        TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros).
+        TF1 variable names, creation order and initialisers (gates bias ones, candidate bias zeros), ``lnlstm`` =
+        tf.contrib.rnn.LayerNormBasicLSTMCell(128): the kernel, then gamma (ones) and beta (zeros) of the scopes
+        input, transform, forget_gate, output, state.
         --rnn_layers: ``layers`` > 1 (gru only) = MultiRNNCell of that many GRUCell(128), each cell's four variables
         in TF1's static_rnn creation order; layers == 1 is the single cell, unchanged.
         --bidirectional (gru, one layer): a forward and a backward GRUCell(128) over the same rows, the head on both
@@ -91,6 +99,13 @@ class LstmModel(ModelDef):
                 self.cells.append(names)
                 self.specs += [VarSpec(names[0], (rows, 2 * H), glorot_uniform_init), VarSpec(names[1], (2 * H,), ones_init),
                                VarSpec(names[2], (rows, H), glorot_uniform_init), VarSpec(names[3], (H,), zeros_init)]
+        elif cell == "lnlstm":
+            # kernel (no bias: TF creates none with layer_norm), then gamma (ones), beta (zeros) per scope
+            pre = "rnn/layer_norm_basic_lstm_cell/"
+            self.kname = pre + "kernel"
+            self.ln_names = [pre + s + "/" + v for s in LN_SCOPES for v in ("gamma", "beta")]
+            self.specs = head + [VarSpec(self.kname, (I + H, 4 * H), glorot_uniform_init)] + [
+                VarSpec(n, (H,), ones_init if n.endswith("gamma") else zeros_init) for n in self.ln_names]
         elif cell == "gru":
             self.gk, self.gb = "rnn/gru_cell/gates/kernel", "rnn/gru_cell/gates/bias"
             self.ck, self.cb = "rnn/gru_cell/candidate/kernel", "rnn/gru_cell/candidate/bias"
@@ -113,7 +128,7 @@ class LstmModel(ModelDef):
 
     def program(self, device, batch_size=None, seed: int = 0):
         cls = (GruBidirProgram if self.bidirectional else GruStackProgram if self.layers > 1
-               else GruProgram if self.cell == "gru" else LstmProgram)
+               else GruProgram if self.cell == "gru" else LnLstmProgram if self.cell == "lnlstm" else LstmProgram)
         return cls(self, device, batch_size or self.default_batch, seed)
 
 
@@ -371,6 +386,84 @@ class GruProgram(StepProgram):
         return {"loss": ScaledScalar(self.loss, 1.0 / B)}
 
     evaluate = LstmProgram.evaluate  # program-batch chunks, padded: uses load_batch / forward / logits / y only
+
+
+class LnLstmProgram(StepProgram):
+    """The row-sequence model with tf.contrib.rnn.LayerNormBasicLSTMCell(128) (LstmModel.set_cell("lnlstm")).
+
+    The ten gamma / beta variables are adjacent 128-float blocks of the flat parameter buffer, so the kernels take them
+    (and their gradients) as ONE [10][128] view.  On the GPU the forward and the BPTT recurrence are one persistent launch
+    each (csrc/kernels/lnlstm_seq.hip, a workgroup per 16 batch rows), the gamma / beta gradients one slab per workgroup
+    summed in a fixed order, and the kernel gradient one wgrad_tallk launch; there is no per-step HIP path, so the
+    batch must be a multiple of 16 there.  On the CPU the same ops run their step-by-step fp32 paths."""
+
+    def __init__(self, model: LstmModel, device, batch_size: int, seed: int = 0):
+        super().__init__(model, device, batch_size, seed)
+        B = batch_size
+        if self.device.type == "cuda" and B % 16:
+            raise ValueError("--cell=lnlstm on the GPU runs whole 16-row groups: batch size %d is not a multiple "
+                             "of 16" % B)
+        f = dict(device=self.device, dtype=torch.float32)
+        self.xh = torch.zeros(T, B, I + H, **f)     # [x_t, h_{t-1}] rows
+        self.zhat = torch.empty(T, B, 4 * H, **f)   # normalised gate pre-activations
+        self.chat = torch.empty(T, B, H, **f)       # normalised cell state
+        self.rs = torch.empty(T, B, 5, **f)         # reciprocal standard deviations
+        self.hT = torch.empty(B, H, **f)
+        self.logits = torch.empty(B, NC, **f)
+        self.y = torch.empty(B, NC, **f)
+        self.dlogits = torch.empty(B, NC, **f)
+        self.dg = torch.empty(T, B, 4 * H, **f)
+        self.ws_ln = torch.empty(max(B // 16, 1), 10, H, **f)  # one gamma / beta gradient slab per workgroup
+        self.loss = torch.zeros(1, **f)
+        self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
+        m, P = model, self.P
+        self.Wo, self.bo, self.K = P.view("Variable"), P.view("Variable_1"), P.view(m.kname)
+        self.gWo, self.gbo, self.gK = P.gview("Variable"), P.gview("Variable_1"), P.gview(m.kname)
+        o = P.offsets[m.ln_names[0]]
+        if [P.offsets[n] for n in m.ln_names] != [o + H * i for i in range(10)]:
+            raise RuntimeError("lnlstm: the gamma / beta variables are not adjacent in the parameter buffer")
+        self.ln, self.gln = P.master[o:o + 10 * H].view(10, H), P.grad[o:o + 10 * H].view(10, H)
+        self.k_splits = 32
+        self.ws_k = None  # the kernel gradient's own split-K workspace
+        if self.device.type == "cuda":
+            self.ws_k = torch.empty(ops.tallk_ws_floats(I + H, 4 * H, self.k_splits), **f)
+
+    load_batch = GruProgram.load_batch  # stages x into xh, zeroes h_{-1}, copies the labels, clears the accumulators
+
+    def forward(self, head=False):
+        """The recurrence, then the classifier head (as GruProgram.forward)."""
+        B = self.batch_size
+        if not ops.lnlstm_seq_fwd(self.xh, self.K, self.ln, self.zhat, self.chat, self.rs, self.hT):
+            raise RuntimeError("lnlstm_seq_fwd declined the shape (B %d, I %d, H %d): no other path" % (B, I, H))
+        if head and ops.dense_head(self.hT, self.Wo, self.bo, self.y, self.logits, self.loss, self.correct,
+                                   self.gWo, self.gbo, None, 1.0 / B, w_fmajor=True, store=True,
+                                   dl_out=self.dlogits):
+            return True
+        ops.gemm(self.hT, self.Wo, self.logits, M=B, N=NC, K=H, bmode=ops.RMAJ, ldb=NC, bias=self.bo)
+        return False
+
+    def compute_grads(self):
+        B = self.batch_size
+        # every gradient element is stored (not accumulated) by this step's kernels
+        if not getattr(self, "_acc_cleared", False):
+            self.loss.zero_()
+            self.correct.zero_()
+        self._acc_cleared = False
+        if not self.forward(head=True):  # a batch too large for the one-workgroup head
+            ops.softmax_xent(self.logits, labels_oh=self.y, scale=1.0 / B, dlogits=self.dlogits, loss_sum=self.loss,
+                             correct=self.correct)
+            ops.gemm(self.hT, self.dlogits, self.gWo, M=H + 1, N=NC, K=B, amode=ops.RMAJ, lda=H, bmode=ops.RMAJ,
+                     ldb=NC, a_ones_row=H, bias_out=self.gbo)
+        # the BPTT launch forms dh_T = dlogits . W_out^T itself (hT stands in for the unused dhT)
+        if not ops.lnlstm_seq_bwd(self.K, self.ln, self.zhat, self.chat, self.rs, self.hT, self.dg, self.gln,
+                                  self.ws_ln, dl=self.dlogits, wo=self.Wo):
+            raise RuntimeError("lnlstm_seq_bwd declined the shape (B %d, I %d, H %d)" % (B, I, H))
+        # kernel gradient over all T*B rows (the cell has no bias)
+        ops.wgrad_tallk(self.xh, I + H, self.dg, 4 * H, I + H, 4 * H, T * B, self.gK, splits=self.k_splits,
+                        workspace=self.ws_k)
+        return {"loss": ScaledScalar(self.loss, 1.0 / B)}
+
+    evaluate = LstmProgram.evaluate  # uses load_batch / forward / logits / y only
 
 
 class GruStackProgram(StepProgram):

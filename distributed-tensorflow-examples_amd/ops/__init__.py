@@ -37,6 +37,7 @@ __all__ = [
     "ema_swap", "ema_decay_value", "ema_update_ref",
     "layer_trust", "layer_trust_plan", "lars_trust_ref", "LARS_CHUNK_MAX",
     "gru_seq_fwd", "gru_seq_bwd", "gru_proj_fwd", "gru_stack_bwd", "gru_bidir_fwd", "gru_bidir_bwd",
+    "lnlstm_seq_fwd", "lnlstm_seq_bwd", "LNLSTM_EPS",
 ]
 
 _TILES = [(1, 128, 128), (2, 128, 64), (3, 64, 128), (0, 64, 64)]
@@ -1754,6 +1755,83 @@ def gru_bidir_bwd(xh, Wg0, Wc0, Wg1, Wc1, g, cand, dhT, dgg, dgc, dl=None, wo=No
     og, oc = torch.empty_like(dgg[1]), torch.empty_like(dgc[1])
     gru_seq_bwd(xh[1].flip(0), Wg1, Wc1, g[1].flip(0), cand[1].flip(0), dhT[:, H:], og, oc, **start(1))
     dgg[1], dgc[1] = og.flip(0), oc.flip(0)
+    return True
+
+
+# ------------------------------------------------- layer-normalised LSTM
+LNLSTM_EPS = 1e-12  # tf.contrib.layers.layer_norm's variance epsilon
+
+
+def _row_norm(v):
+    """(v - mean) * rstd over the last axis (biased, centred variance) and rstd"""
+    d = v - v.mean(-1, keepdim=True)
+    r = torch.rsqrt((d * d).mean(-1, keepdim=True) + LNLSTM_EPS)
+    return d * r, r.squeeze(-1)
+
+
+def lnlstm_seq_fwd(xh, K, ln, zhat, chat, rs, hT, forget_bias=1.0) -> bool:
+    """Whole-sequence TF1 LayerNormBasicLSTMCell forward.  xh [T][B][I+H] holds x_t in its first I columns and h_{-1} in
+    the h columns of step 0 (c_{-1} = 0); K [I+H][4H] (gates i, j, f, o; no bias); ln [10][H]: rows 2k, 2k + 1 = gamma,
+    beta of k = i, j, f, o, state.  Written: the h_{t-1} columns of steps 1.., zhat [T][B][4H] and chat [T][B][H] (the
+    normalised gate pre-activations and cell state, before gamma / beta), rs [T][B][5] (their reciprocal standard
+    deviations), hT [B][H].  GPU: one persistent launch (lnlstm_seq.hip); False, with nothing written, outside H = 128,
+    I = 28, B % 16 == 0.  CPU: fp32, step by step."""
+    if xh.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.lnlstm_seq_fwd(xh, K, ln, zhat, chat, rs, hT, float(forget_bias)))
+    T, B, H = xh.shape[0], xh.shape[1], hT.shape[1]
+    I = xh.shape[2] - H
+    g, b = ln[0:8:2], ln[1:8:2]  # [4][H]
+    h, c = xh[0, :, I:].clone(), torch.zeros(B, H)
+    for t in range(T):
+        if t > 0:
+            xh[t, :, I:] = h
+        zh, r = _row_norm((xh[t] @ K).view(B, 4, H))
+        zhat[t], rs[t, :, :4] = zh.reshape(B, 4 * H), r
+        y = zh * g + b
+        ct = c * torch.sigmoid(y[:, 2] + forget_bias) + torch.sigmoid(y[:, 0]) * torch.tanh(y[:, 1])
+        chat[t], rs[t, :, 4] = _row_norm(ct)
+        c = ln[8] * chat[t] + ln[9]
+        h = torch.tanh(c) * torch.sigmoid(y[:, 3])
+    hT.copy_(h)
+    return True
+
+
+def lnlstm_seq_bwd(K, ln, zhat, chat, rs, dhT, dg, dln, ws=None, dl=None, wo=None, forget_bias=1.0) -> bool:
+    """Whole-sequence BPTT from lnlstm_seq_fwd's zhat / chat / rs: dg [T][B][4H], the gradient of the raw gate
+    pre-activations (the kernel gradient is xh^T dg), and dln [10][H], the gradient of ln.  dh_T is dhT, or dl . wo^T when
+    the head's dlogits dl [B][NC] and W_out wo [H][NC] are given.  GPU: one persistent launch that leaves one [10][H]
+    slab per 16 rows in ``ws`` [B/16][10][H] plus a fixed-order slab sum (bitwise reproducible); False as for
+    lnlstm_seq_fwd.  CPU: fp32, step by step (ws unused)."""
+    if chat.is_cuda:
+        require()
+        return bool(torch.ops.dtfe_rnn.lnlstm_seq_bwd(K, ln, zhat, chat, rs, dhT, dg, dln, ws, dl, wo,
+                                                      float(forget_bias)))
+    T, B, H = chat.shape
+    Kh, g, b = K[K.shape[0] - H:], ln[0:8:2], ln[1:8:2]
+    dh, dc = (dhT if dl is None else dl @ wo.t()), torch.zeros(B, H)
+    dln.zero_()
+
+    def ln_bwd(d, n, r):  # through n = (v - mean) * rstd: d loss / d v
+        return r.unsqueeze(-1) * (d - d.mean(-1, keepdim=True) - n * (d * n).mean(-1, keepdim=True))
+
+    for t in range(T - 1, -1, -1):
+        zh = zhat[t].view(B, 4, H)
+        y = zh * g + b
+        si, tj, sf, so = torch.sigmoid(y[:, 0]), torch.tanh(y[:, 1]), torch.sigmoid(y[:, 2] + forget_bias), torch.sigmoid(y[:, 3])
+        tc = torch.tanh(ln[8] * chat[t] + ln[9])
+        cp = ln[8] * chat[t - 1] + ln[9] if t > 0 else torch.zeros(B, H)
+        dc = dc + dh * so * (1 - tc * tc)
+        dln[8] += (dc * chat[t]).sum(0)
+        dln[9] += dc.sum(0)
+        dct = ln_bwd(dc * ln[8], chat[t], rs[t, :, 4])
+        dy = torch.stack([dct * tj * si * (1 - si), dct * si * (1 - tj * tj), dct * cp * sf * (1 - sf),
+                          dh * tc * so * (1 - so)], 1)
+        dln[0:8:2] += (dy * zh).sum(0)
+        dln[1:8:2] += dy.sum(0)
+        dg[t] = ln_bwd(dy * g, zh, rs[t, :, :4]).reshape(B, 4 * H)
+        dc = dct * sf
+        dh = dg[t] @ Kh.t()
     return True
 
 

@@ -977,10 +977,11 @@ def run(model_name: str, argv=None, log=_print):
             model.set_cell(flags.cell, flags.rnn_layers, flags.bidirectional)
         except ValueError as e:
             raise SystemExit(str(e))
-        if flags.cell == "gru" and flags.device != "cpu" and torch.cuda.is_available() and flags.batch_size % 16:
-            # refused here with a message (GruProgram refuses it again when it is built: no per-step GRU path)
-            raise SystemExit("--cell=gru on the GPU runs whole 16-row groups: --batch_size=%d is not a multiple of 16"
-                             % flags.batch_size)
+        if (flags.cell in ("gru", "lnlstm") and flags.device != "cpu" and torch.cuda.is_available()
+                and flags.batch_size % 16):
+            # refused here with a message (the program refuses it again when it is built: no per-step path)
+            raise SystemExit("--cell=%s on the GPU runs whole 16-row groups: --batch_size=%d is not a multiple of 16"
+                             % (flags.cell, flags.batch_size))
     elif flags.cell != "lstm":
         raise SystemExit("--cell=%s: only the lstm example has a recurrent cell (model %r)" % (flags.cell, model.name))
     elif flags.rnn_layers != 1:

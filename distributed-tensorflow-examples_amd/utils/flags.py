@@ -110,9 +110,10 @@ def build_parser(model_defaults: dict | None = None, prog=None):
                     help="compute dtype: fp32 = exact-fp32 MFMA kernels and fp32 activations (the reference's "
                          "precision), bf16 = bf16 MFMA with fp32 accumulation / masters; auto = the model's default. "
                          "GAN / autoencoder / LSTM / softmax: fp32 only; CNN: bf16 (default) or fp32; ResNets: bf16")
-    ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm",
+    ap.add_argument("--cell", choices=["lstm", "gru", "lnlstm"], default="lstm",
                     help="recurrent cell of the LSTM example: lstm = BasicLSTMCell(128) (the reference), gru = "
-                         "tf.nn.rnn_cell.GRUCell(128) on its own persistent kernels (GPU: batch a multiple of 16)")
+                         "tf.nn.rnn_cell.GRUCell(128), lnlstm = tf.contrib.rnn.LayerNormBasicLSTMCell(128); gru and "
+                         "lnlstm run on their own persistent kernels (GPU: batch a multiple of 16)")
     ap.add_argument("--rnn_layers", type=int, default=1,
                     help="recurrent layers of the LSTM example (1-4): L > 1 stacks L GRUCell(128) like TF1's "
                          "MultiRNNCell (variables rnn/multi_rnn_cell/cell_<l>/gru_cell/...) and needs --cell gru")
